@@ -16,9 +16,15 @@ step.  The weak form (every rank a full C4-size shard of an N·1000-keyframe tra
 N = 1 the step of a 1/8 shard under "shard8" (the strong-scaling ceiling at N = 8).  Timing: a clock warm-up, W warmup
 steps, then exactly K steps bracketed by barrier + synchronize.
 
-Also reported: the block kernel's roofline position (algorithmic bytes ÷ HIP-event-timed kernel duration on the engine
-stream); the CPU baseline — the reference's CPU path, real Ceres 2.0.0 (built from the reference's vendored sources
-by oracle/ceres.mk) evaluating AutoDiff cost functions with its ProgramEvaluator on this host's cores, timed by its
+A plain run (`--gpus N --steps K --warmup W`) does that and nothing else: it sets the problem up, warms up, times the K
+steps, writes the last step's outputs when `--dump-outputs DIR` is given and prints the result line; the block kernel's
+roofline position in it comes from the timed steps themselves (algorithmic bytes ÷ the HIP-event-timed duration on the
+engine stream; `traffic` from the committed profile of the same workload).  Everything below runs under `--full` only
+(its fields are null in a plain run's line).
+
+Also reported under --full: the block kernel's measured HBM traffic (two rocprofv3 passes) and the chip's streaming
+rate beside the roofline figures; the per-launch-event diagnostic run; the weak-scaling and 1/8-shard legs; the CPU
+baseline — the reference's CPU path, real Ceres 2.0.0 (built from the reference's vendored sources by oracle/ceres.mk) evaluating AutoDiff cost functions with its ProgramEvaluator on this host's cores, timed by its
 own "Jacobian & residual evaluation" timer on a bounded sample of the same workload; ms per LM iteration of the
 on-device Gauss-Newton (C4 on rendered images — the solve the GPU tests pin against real Ceres, whose trajectory on the
 same problem is reported beside it — and C3 = configs[2] in "gn_c3"); and the C5-style 21-px / fp16 / pyramid leg.
@@ -251,13 +257,14 @@ def make_states(pb, torch, dev, seed):
     return states
 
 
-def time_evaluation(eng, states, steps, warmup, clock_warmup_s, torch, dist, dev):
+def time_evaluation(eng, states, steps, warmup, clock_warmup_s, torch, dist, dev, diagnostics=True):
     """W warmup steps (after a clock warm-up), then K timed steps bracketed by barrier + synchronize (enqueued by one
     pba_evaluate_states_device call: K launches, one per step, each at a new HBM-resident state); returns
     (max-over-ranks elapsed s, max-over-ranks average block-kernel µs, host diagnostics).  The kernel duration comes
     from two HIP events on the engine's stream around the K timed launches (elapsed ÷ K: each launch plus the
     dispatch gap to the next, so never below rocprof's kernel average); the launches themselves carry no events —
-    a pair of timing events per launch idles the GPU ~4 µs per step (`host` reports that instrumented run too)."""
+    a pair of timing events per launch idles the GPU ~4 µs per step (with `diagnostics`, `host` reports such an
+    instrumented run of the same K steps too, made between the warm-up and the timed region)."""
     def step(i):  # one launch: pairs formed in the block prologue, state adopted by the same launch
         p, r = states[i & 1]
         eng.evaluate_state_device(p.data_ptr(), r.data_ptr(), True, sync=False)
@@ -274,19 +281,21 @@ def time_evaluation(eng, states, steps, warmup, clock_warmup_s, torch, dist, dev
     for i in range(warmup):
         step(i)
     eng.synchronize()
-    # diagnostic (not the metric): the same steps with a timing-event pair around every launch (the engine's
-    # per-launch kernel timing: kernel-only durations)
-    eng.enable_kernel_timing(True)
-    eng.kernel_timing()  # reset
-    t0 = time.perf_counter()
-    for i in range(steps):
-        step(i)
-    eng.synchronize()
-    t_ev = time.perf_counter() - t0
-    kern_only_ms, launches = eng.kernel_timing()
-    eng.enable_kernel_timing(False)
-    host_diag = {"us_per_step_with_per_launch_events": 1e6 * t_ev / steps,
-                 "kernel_only_us_per_launch_events": 1e3 * kern_only_ms / max(launches, 1)}
+    host_diag = {}
+    if diagnostics:
+        # diagnostic (not the metric): the same steps with a timing-event pair around every launch (the engine's
+        # per-launch kernel timing: kernel-only durations)
+        eng.enable_kernel_timing(True)
+        eng.kernel_timing()  # reset
+        t0 = time.perf_counter()
+        for i in range(steps):
+            step(i)
+        eng.synchronize()
+        t_ev = time.perf_counter() - t0
+        kern_only_ms, launches = eng.kernel_timing()
+        eng.enable_kernel_timing(False)
+        host_diag = {"us_per_step_with_per_launch_events": 1e6 * t_ev / steps,
+                     "kernel_only_us_per_launch_events": 1e3 * kern_only_ms / max(launches, 1)}
     # the timed region
     stream = torch.cuda.ExternalStream(eng.stream(), device=dev)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -489,6 +498,25 @@ def c5_eval(pb, images, states, steps, warmup, clock_warmup_s, torch, dev_index,
             "pyramid_build_ms": pyr_ms, "gn": gn}
 
 
+DUMP_BLOCKS = 100000  # --dump-outputs: records of this many blocks (45 MB at the headline's 112 floats per record)
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the last timed step left for a caller of the timed path (pba_get_records,
+    pba_get_block_costs), as float32 .npy files: `records` ([r | J_h | J_t | J_ρ] per block) for a fixed, seeded sample
+    of DUMP_BLOCKS blocks in ascending order (every block when there are no more), their indices in `record_blocks`
+    (float64), and `block_costs` and `valid` (0 / 1) for every block."""
+    rec, valid = eng.records()
+    costs = eng.block_costs()
+    n = rec.shape[0]
+    sel = np.arange(n) if n <= DUMP_BLOCKS else np.sort(np.random.default_rng(20240607).choice(n, DUMP_BLOCKS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "records.npy"), np.ascontiguousarray(rec[sel], np.float32))
+    np.save(os.path.join(out_dir, "record_blocks.npy"), sel.astype(np.float64))
+    np.save(os.path.join(out_dir, "block_costs.npy"), costs.astype(np.float32))
+    np.save(os.path.join(out_dir, "valid.npy"), valid.astype(np.float32))
+
+
 HEADLINE_KERNEL = "photometric_block_kernel<0, 8, 1, float>"
 
 
@@ -611,6 +639,13 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--clock-warmup-s", type=float, default=0.3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's records, block costs "
+                         "and validity flags) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (live HBM traffic, streaming rate, per-launch-event diagnostic, "
+                         "weak / 1/8-shard steps, CPU baseline, C2 drop-in, GN on C4 and C3, C5); the --no-* and "
+                         "--cpu-seconds / --gn-iterations options below shape those legs")
     ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--points", type=int, default=100000)
     ap.add_argument("--targets", type=int, default=4)
@@ -661,16 +696,21 @@ def main():
     eng = engine_mod.Engine(synth.PHOTOMETRIC, synth.PINHOLE, device=dev_index, huber_width=9.0)
     eng.set_problem(pb, images_device_ptr=images.data_ptr())
     states = make_states(pb, torch, dev, 7)
-    eng.set_state_device(states[0][0].data_ptr(), states[0][1].data_ptr())
-    eng.evaluate(True)
-    _, valid = eng.records()
-    elapsed, kern_us, host_diag = time_evaluation(eng, states, args.steps, args.warmup, args.clock_warmup_s, torch, dd, dev)
+    valid = None
+    if args.full:  # the valid-block count of the result line's config: one evaluation and read-back ahead of the timing
+        eng.set_state_device(states[0][0].data_ptr(), states[0][1].data_ptr())
+        eng.evaluate(True)
+        _, valid = eng.records()
+    elapsed, kern_us, host_diag = time_evaluation(eng, states, args.steps, args.warmup, args.clock_warmup_s, torch, dd, dev,
+                                                  diagnostics=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
     eng.close()
     kern_us_max = float(all_reduce_max(torch, dd, [kern_us], dev)[0])
 
     # ---- N > 1: the weak form beside it — every rank a full C4-size shard of one N·F-keyframe trajectory ---------------
     weak = None
-    if world > 1:
+    if world > 1 and args.full:
         pw, images_w = synth.c4_shard(dev, rank=rank, world=world, n_frames=F, n_points=Np, K=K)
         ew = engine_mod.Engine(synth.PHOTOMETRIC, synth.PINHOLE, device=dev_index, huber_width=9.0)
         ew.set_problem(pw, images_device_ptr=images_w.data_ptr())
@@ -683,7 +723,7 @@ def main():
                 "note": f"weak scaling: rank r evaluates host keyframes [r*{F}, (r+1)*{F}) of one {world * F + K}-keyframe "
                         f"trajectory ({pw.n_blocks} blocks per GPU), no data-path collective"}
     shard8 = None
-    if world == 1 and not args.no_shard_leg:  # one rank's step of the C4 problem split 8 ways, on this GPU
+    if world == 1 and args.full and not args.no_shard_leg:  # one rank's step of the C4 problem split 8 ways, on this GPU
         p8, _, _ = D.shard_problem(full, 8, 0)
         e8 = engine_mod.Engine(synth.PHOTOMETRIC, synth.PINHOLE, device=dev_index, huber_width=9.0)
         e8.set_problem(p8, images_device_ptr=images.data_ptr())
@@ -699,7 +739,7 @@ def main():
 
     # ---- the Gauss-Newton leg: the C4 problem with rendered images (the solve the GPU tests pin against real Ceres) ----
     gn = None
-    if args.gn_iterations > 0:
+    if args.full and args.gn_iterations > 0:
         gfull, gimages = synth.c4_shard(dev, n_frames=F, n_points=Np, K=K, texture="render")
         gpb = D.shard_problem(gfull, world, rank)[0] if world > 1 else gfull
         eng = engine_mod.Engine(synth.PHOTOMETRIC, synth.PINHOLE, device=dev_index, huber_width=9.0)
@@ -718,10 +758,10 @@ def main():
         del gimages
 
     c3 = None
-    if world == 1 and not args.no_c3 and args.gn_iterations > 0:
+    if world == 1 and args.full and not args.no_c3 and args.gn_iterations > 0:
         c3 = gn_c3(args.gn_iterations, torch, dev_index, dev)
     c5 = None
-    if world == 1 and not args.no_c5:
+    if world == 1 and args.full and not args.no_c5:
         c5 = c5_eval(full, images, states, args.steps, args.warmup, args.clock_warmup_s, torch, dev_index, dev,
                      args.gn_iterations)
 
@@ -732,7 +772,7 @@ def main():
         bpb = algorithmic_bytes_per_block(pb.P, K, pb.n_frames, pb.n_points, pb.n_blocks)
         achieved = bpb * pb.n_blocks / (kern_us * 1e-6) / 1e9
         traffic, traffic_info = None, None
-        if world == 1 and not args.no_live_traffic:
+        if world == 1 and args.full and not args.no_live_traffic:
             traffic, traffic_info = measure_traffic(args, pb.n_blocks)
         if traffic is None:  # fall back to the committed profile of the same workload
             reason = traffic_info
@@ -748,7 +788,7 @@ def main():
                     traffic = None
         cpu = None
         c2 = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             images_host = images.cpu().numpy()
             cpu = cpu_baseline(full, images_host, args.cpu_seconds)
             if not args.no_c2:
@@ -756,7 +796,7 @@ def main():
                     c2 = c2_dropin(full, images_host, host_cores()["usable"])
                 except Exception as ex:  # a secondary leg: report it, keep the headline line
                     c2 = {"error": f"{type(ex).__name__}: {ex}"[:300]}
-        stream_peak = stream_copy_peak(torch, dev, achieved)
+        stream_peak = stream_copy_peak(torch, dev, achieved) if args.full else {}
         # the GN leg's collective, as the leg chooses it (torch.distributed between trials unless PBA_BENCH_GN_COMM=1)
         gn_comm = ("device-steered RCCL loop" if world > 1 and dist.get_backend() == "nccl"
                    and os.environ.get("PBA_BENCH_GN_COMM", "0") == "1" else "torch.distributed between trials")
@@ -767,6 +807,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "strong",
@@ -779,7 +820,7 @@ def main():
                             (f", split by host keyframe over {world} GPUs (rank 0: {pb.n_blocks} blocks)" if world > 1 else "") +
                             "; one step = full r + tangent-J evaluation (Ceres-mode records) at a new HBM-resident state",
                 "keyframes": F, "points": Np, "patch": pb.P, "targets_per_point": K,
-                "blocks_total": total_blocks, "blocks_rank0": pb.n_blocks, "valid_blocks_rank0": int(valid.sum()),
+                "blocks_total": total_blocks, "blocks_rank0": pb.n_blocks, "valid_blocks_rank0": None if valid is None else int(valid.sum()),
                 "parallelism": f"host-keyframe shards x{world} (evaluation: no data-path collective; "
                                + (f"GN: all-reduce of the reduced camera system — {gn_comm})" if world > 1
                                   else "GN: one GPU)"),

@@ -33,6 +33,39 @@ def test_counter_bytes_per_launch_sums_dimensions_and_averages_dispatches():
     assert b.counter_bytes_per_launch(rows, "GRBM_COUNT", k) is None
 
 
+def test_dump_outputs_writes_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs at the headline's size (400k blocks x 112 floats): float32 / float64 .npy files, at most 64 MB in
+    all, the same seeded sample of blocks on every call."""
+    import numpy as np
+    b = _bench()
+
+    class FakeEngine:
+        n, rec = 400000, 112
+
+        def records(self):
+            r = np.arange(self.n, dtype=np.float32)[:, None] + np.zeros((1, self.rec), np.float32)
+            return r, (np.arange(self.n) % 7 != 0).astype(np.uint8)
+
+        def block_costs(self):
+            return np.arange(self.n, dtype=np.float32) * 0.5
+
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        b.dump_outputs(FakeEngine(), d)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["block_costs.npy", "record_blocks.npy", "records.npy", "valid.npy"]
+    arrays = {n: np.load(os.path.join(dirs[0], n)) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 1000 * 1000
+    for n in names:
+        assert np.array_equal(arrays[n], np.load(os.path.join(dirs[1], n)))
+    sel = arrays["record_blocks.npy"].astype(np.int64)
+    assert sel.shape == (b.DUMP_BLOCKS,) and np.all(np.diff(sel) > 0) and sel[-1] < 400000
+    assert np.array_equal(arrays["records.npy"][:, 0], sel.astype(np.float32))  # the sampled blocks' own records
+    assert arrays["valid.npy"].shape == (400000,) and set(np.unique(arrays["valid.npy"])) == {0.0, 1.0}
+    assert np.array_equal(arrays["block_costs.npy"], np.arange(400000, dtype=np.float32) * 0.5)
+
+
 def test_algorithmic_bytes_per_block_at_c4():
     b = _bench()
     # DESIGN.md §3: 517.3 B at P = 8, K = 4 on the C4 problem

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Condense rocprofv3 outputs under gpurun_out/ into the small, committed summaries under profiles/.
+"""Condense rocprofv3 outputs under tools/gpu_check.sh's $OUT (default bench_out/) into the small, committed summaries under profiles/.
 
 usage: tools/prof_summary.py <tag> <out_prefix>
-  reads  gpurun_out/prof_<tag>_kt/run_kernel_stats.csv          (--kernel-trace --stats)
-         gpurun_out/prof_<tag>_<COUNTER>/run_counter_collection.csv  (one --pmc pass per counter)
+  reads  $OUT/prof_<tag>_kt/run_kernel_stats.csv          (--kernel-trace --stats)
+         $OUT/prof_<tag>_<COUNTER>/run_counter_collection.csv  (one --pmc pass per counter)
   writes profiles/<out_prefix>_kernel_stats.csv  (engine kernels only, names shortened)
          profiles/<out_prefix>_pmc.csv           (per-kernel mean counter values per dispatch)
          profiles/traffic_<kernel>.json          (HBM bytes per launch = (FETCH_SIZE + WRITE_SIZE)·1024)
@@ -17,6 +17,7 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.path.join(ROOT, os.environ.get("OUT", "bench_out"))
 OURS = re.compile(r"(photometric_block_kernel|geometric_block_kernel|pair_kernel|cr_\w+|assemble\w*|band_\w+|"
                   r"skyline\w*|schur_\w+|linearize\w*|update\w*|reduce\w*|lm_\w+|dist_\w+|intr_\w+|export\w*|import\w*|pyramid\w*|"
                   r"__amd_rocclr_copyBuffer)")
@@ -39,7 +40,7 @@ def main(tag, prefix):
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     # per (kernel, grid size) from the kernel trace: one kernel runs at several sizes in a bench run (the C4 launch,
     # the 1/8 shard, the strong-scaling shard), and rocprofv3's own stats average them together
-    kt = os.path.join(ROOT, "gpurun_out", f"prof_{tag}_kt", "run_kernel_trace.csv")
+    kt = os.path.join(OUT, f"prof_{tag}_kt", "run_kernel_trace.csv")
     durs = collections.defaultdict(list)
     for r in csv.DictReader(open(kt)):
         if OURS.search(r["Kernel_Name"]):
@@ -53,7 +54,7 @@ def main(tag, prefix):
             sd = (sum((x - m) ** 2 for x in d) / len(d)) ** 0.5
             w.writerow([k, g, len(d), sum(d), f"{m:.1f}", min(d), max(d), f"{sd:.1f}"])
     pmc = collections.defaultdict(dict)
-    for d in glob.glob(os.path.join(ROOT, "gpurun_out", f"prof_{tag}_*", "run_counter_collection.csv")):
+    for d in glob.glob(os.path.join(OUT, f"prof_{tag}_*", "run_counter_collection.csv")):
         agg = collections.defaultdict(list)
         for r in csv.DictReader(open(d)):
             if OURS.search(r["Kernel_Name"]):
