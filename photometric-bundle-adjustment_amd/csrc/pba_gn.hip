@@ -3520,6 +3520,7 @@ __global__ __launch_bounds__(256) void intr_rows_kernel(const IntrRowsArgs a) {
   } else {
     row0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);
     nrow = min(64, a.n - row0);
+    if (nrow <= 0) return;  // (whole waves: the last workgroup's waves past the end — rec has a.n entries)
   }
   if (lm_view(a.lm).done != 0.0) return;       // (uniform)
   const int gb = row0 + max(min(lane, nrow - 1), 0);  // every lane of a wave takes part in its stores
@@ -5677,11 +5678,16 @@ void enqueue_border(pba_engine* e, double lambda, const double* lm, double* X, b
 #ifndef PBA_INTR_KPW_BIG
 #define PBA_INTR_KPW_BIG 2
 #endif
-  const int kpw = nf * G.nc_sys < 512 ? 4 : PBA_INTR_KPW_BIG;  // waves per keyframe block (border_keyframes)
+  bool fused = nf * G.nc_sys < 512;  // one launch (below) while the keyframe part is small, else three
+  if (const char* tb = test_hook("PBA_TEST_BORDER")) {  // (tests: "fused" / "split" whatever the size)
+    if (!std::strcmp(tb, "fused")) fused = true;
+    else if (!std::strcmp(tb, "split")) fused = false;
+  }
+  const int kpw = fused ? 4 : PBA_INTR_KPW_BIG;  // waves per keyframe block (border_keyframes)
   double* dpart = G.ib_part.p;
   double* spart = dpart + (size_t)G.nc_sys * kCamSplit * kCamDir;
   const int nk_x = (nf * kpw + 3) / 4, ncp = G.nc_sys * (G.nc_sys + 1) / 2;
-  if (nf * G.nc_sys < 512) {
+  if (fused) {
     const int n_wg = nk_x * G.nc_sys + kCamSplit * (G.nc_sys + ncp);
     intr_border_all_kernel<<<n_wg, 256, 0, e->stream>>>(ba, lambda, kpw, nk_x, dpart, spart);
   } else {

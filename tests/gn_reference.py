@@ -332,7 +332,9 @@ def linearize_intrinsics(pb, poses, rho, intr, a, fixed=()):
     """Geometric blocks with the TARGET camera's intrinsics free (optimize_intrinsics, map_utils.h:339-345; the functor's
     sIntr_c2 block, reprojection.h:83-86): H (N×N), g, cost with N = 6·n_frames + 8·n_cams + n_points (unknowns in that
     order), from the oracle's 44-value records (orc_evaluate_intrinsics: projection with `intr`, host unprojection with
-    pb.intrinsics); fixed frames' columns zeroed."""
+    pb.intrinsics); fixed frames' columns zeroed.  Each block adds only its nonzero columns (host 6, target 6, camera 8,
+    point 1: a 21 × 21 product scattered with np.ix_), so split-border sizes (128 keyframes × 1300 points) take a
+    fraction of a second; tests/test_gn_reference.py holds it to the dense per-block accumulation."""
     rec, valid = O.evaluate_intrinsics(pb, intr, poses=poses, rho=rho)
     r, Jh, Jt, Jr = O.split_record(rec[:, :28], 2)
     Ji = rec[:, 28:44].reshape(-1, 2, 8)
@@ -346,21 +348,25 @@ def linearize_intrinsics(pb, poses, rho, intr, a, fixed=()):
     fixed = set(int(f) for f in fixed)
     H = np.zeros((N, N))
     g = np.zeros(N)
+    six, eight = np.arange(6), np.arange(8)
     for b in range(pb.n_blocks):
         if w[b] == 0:
             continue
         p = pb.block_point[b]
         h, t = pb.point_host[p], pb.block_target[b]
         c = pb.frame_cam[t]
-        J = np.zeros((2, N))
+        cols, parts = [], []
         if h not in fixed:
-            J[:, 6 * h:6 * h + 6] = Jh[b]
+            cols.append(6 * h + six)
+            parts.append(Jh[b])
         if t not in fixed:
-            J[:, 6 * t:6 * t + 6] = Jt[b]
-        J[:, K0 + 8 * c:K0 + 8 * c + 8] = Ji[b]
-        J[:, K0 + 8 * nc + p] = Jr[b]
-        H += w[b] * J.T @ J
-        g += w[b] * J.T @ r[b]
+            cols.append(6 * t + six)
+            parts.append(Jt[b])
+        cols += [K0 + 8 * c + eight, np.array([K0 + 8 * nc + p])]
+        parts += [Ji[b], Jr[b][:, None]]
+        idx, J = np.concatenate(cols), np.concatenate(parts, axis=1)
+        H[np.ix_(idx, idx)] += w[b] * J.T @ J
+        g[idx] += w[b] * J.T @ r[b]
     return H, g, cost
 
 

@@ -441,8 +441,21 @@ def test_free_intrinsics_exchange_matches_single_engine_step(world, model, lam):
     the direct diagonal, g, observed cameras) after the band; the importer builds the summed skyline system (band K +
     border) and solves it with its active front in LDS.  Every rank's pose step, candidate intrinsics and point steps
     equal the single engine's (pinhole, double sphere, EUCM, KB4)."""
-    import torch
     pb, state = intrinsics_problem(14, 200, 23, model)
+    check_free_intrinsics_exchange(pb, state, world, lam)
+
+
+def test_free_intrinsics_exchange_at_split_border_size():
+    """The same exchange at the smallest size where enqueue_border takes its three-launch branch (nf·nc = 256·2 = 512:
+    intr_border_kernel with two waves per keyframe block, intr_cam_dir_kernel, intr_cam_sch_kernel) on every rank: the
+    export (X ≠ nullptr) through the split kernels, summed over two ranks, against the single engine's step."""
+    pb, state = intrinsics_problem(256, 2600, 27)
+    assert pb.n_frames * pb.intrinsics.shape[0] >= 512
+    check_free_intrinsics_exchange(pb, state, 2, 1e-3)
+
+
+def check_free_intrinsics_exchange(pb, state, world, lam):
+    import torch
     fixed = (0, 1)
     with intrinsics_engine(pb, state, fixed) as full:
         c_full = full.gn_linearize()

@@ -507,12 +507,12 @@ def _intrinsics_rig(n_frames, n_points, seed, n_cams, model=0):
     return pb, intr * np.array([1.003, 0.998, 1.0005, 0.9995, 1, 1, 1, 1])
 
 
-@pytest.mark.parametrize("n_cams", [1, 2, 4])
+@pytest.mark.parametrize("n_cams", [1, 2, 3, 4])
 @pytest.mark.parametrize("lam", [1e-4, 1e-1])
 def test_arrow_and_front_solvers_agree(n_cams, lam, monkeypatch):
     """Free intrinsics (map_utils.h:339-345): the reduced system is an arrow — the keyframes' band plus the 2·nc border
     frames' dense rows.  arrow_solve (parallel cyclic reduction of the band with the border's 12·nc columns as extra
-    right-hand sides in batches of 16 — 1, 2 and 4 batches here — then the border's Schur complement) and
+    right-hand sides in batches of 16 — 1, 2, 3 and 4 batches here — then the border's Schur complement) and
     front_solve_kernel (the skyline Cholesky, border last: the same elimination order; PBA_SOLVER=front) give the same
     pose, intrinsics and inverse-distance steps and model decrease to fp64 rounding."""
     pb, state = _intrinsics_rig(23, 260, 31 + n_cams, n_cams)
@@ -535,7 +535,7 @@ def test_arrow_and_front_solvers_agree(n_cams, lam, monkeypatch):
         assert err <= 1e-8, (name, err)
 
 
-@pytest.mark.parametrize("n_cams", [1, 2, 4])
+@pytest.mark.parametrize("n_cams", [1, 2, 3, 4])
 def test_point_sums_in_rows_match_separate_kernel(n_cams, monkeypatch):
     """Free intrinsics: the points' W sums (per camera Σ W_i, and W_h) are formed by intr_rows_kernel itself when every
     GN point fits one wave (point-aligned waves of ≤ 64 blocks), else by intr_pw_kernel after 64-block waves
@@ -710,6 +710,200 @@ def test_free_intrinsics_reduced_system_and_step(model, lam):
     assert eS <= 1e-5 and eg <= 1e-5, (eS, eg)
     assert ep <= 1e-3 and el <= 1e-3, (ep, el)
     assert abs(m - m_ref) <= 1e-3 * abs(m_ref)
+
+
+_INTR_REF = {}  # rig → (pb, state, (H, g, cost)): the fp64 linearisation, formed once per rig and left unchanged
+
+
+def _intrinsics_rig_reference(n_frames, n_points, seed, n_cams, model=0):
+    key = (n_frames, n_points, seed, n_cams, model)
+    if key not in _INTR_REF:
+        pb, state = _intrinsics_rig(n_frames, n_points, seed, n_cams, model)
+        _INTR_REF[key] = (pb, state, GR.linearize_intrinsics(pb, pb.poses, pb.rho, state, 1.0, (0, 1)))
+    return _INTR_REF[key]
+
+
+def _check_free_intrinsics_step(label, pb, state, lam, lin, library=None):
+    """One free-intrinsics step of the engine (fixed frames 0 and 1, Huber 1.0) against the fp64 reference's, with the
+    comparisons and tolerances of test_free_intrinsics_reduced_system_and_step: cost 1e-6; S and g (through
+    intrinsics_system_index) 1e-5 of their scale; the pads; pose + intrinsics step, δρ and model decrease 1e-3.  Prints
+    and returns the measured errors."""
+    fixed = (0, 1)
+    nf, nc = pb.n_frames, pb.intrinsics.shape[0]
+    H, g, c_ref = lin
+    S_ref, gS_ref, df_ref, dl_ref, m_ref = GR.schur_step_intrinsics(H, g, nf, nc, lam, fixed)
+    with make_engine(pb, 1.0, fixed, library) as eng:
+        eng.set_optimize_intrinsics(True)
+        eng.set_intrinsics_state(state)
+        c = eng.gn_linearize()
+        m, st = eng.gn_step(lam)
+        assert st == 0
+        assert eng.gn_system_size() == 6 * nf + 12 * nc
+        S, gs = eng.gn_reduced_system()
+        dp, dr = eng.gn_last_step()
+        eng.gn_accept()
+        k_new = eng.get_intrinsics()
+    idx = GR.intrinsics_system_index(nf, nc)
+    Ss, gss = S[np.ix_(idx, idx)], gs[idx]
+    err = {"cost": abs(c - c_ref) / c_ref,
+           "S": np.abs(Ss - S_ref).max() / np.abs(S_ref).max(),
+           "g": np.abs(gss - gS_ref).max() / np.abs(gS_ref).max(),
+           "step": np.linalg.norm(np.concatenate([dp.ravel(), (k_new - state).ravel()]) - df_ref) / np.linalg.norm(df_ref),
+           "drho": np.linalg.norm(dr - dl_ref) / np.linalg.norm(dl_ref),
+           "model": abs(m - m_ref) / abs(m_ref)}
+    print(f"\n{label} λ={lam}: " + " ".join(f"{k} {v:.2e}" for k, v in err.items()))
+    pad = np.concatenate([6 * nf + 12 * c + np.arange(8, 12) for c in range(nc)])
+    assert np.allclose(S[np.ix_(pad, pad)], np.eye(len(pad)) * (1 + lam)) and not gs[pad].any()
+    assert err["cost"] <= 1e-6, err
+    assert err["S"] <= 1e-5 and err["g"] <= 1e-5, err
+    assert err["step"] <= 1e-3 and err["drho"] <= 1e-3, err
+    assert err["model"] <= 1e-3, err
+    return err
+
+
+def _free_intrinsics_step(pb, state, lam, library=None):
+    """(pose step, δρ, intrinsics step, [model decrease]) of one free-intrinsics step, fixed frames 0 and 1."""
+    with make_engine(pb, 1.0, (0, 1), library) as eng:
+        eng.set_optimize_intrinsics(True)
+        eng.set_intrinsics_state(state)
+        eng.gn_linearize()
+        m, st = eng.gn_step(lam)
+        assert st == 0
+        dp, dr = eng.gn_last_step()
+        eng.gn_accept()
+        return dp, dr, eng.get_intrinsics() - state, np.array([m])
+
+
+def _assert_same_step(label, a, b, bound):
+    worst = 0.0
+    for name, x, y in zip(("poses", "rho", "intrinsics", "model"), a, b):
+        err = np.linalg.norm(x - y) / np.linalg.norm(y)
+        print(f"\n{label}: {name} {err:.2e}")
+        assert err <= bound, (label, name, err)
+        worst = max(worst, err)
+    return worst
+
+
+# (keyframes, points, cameras, camera model): the smallest rigs with nf·nc ≥ 512 (512 and 513) — enqueue_border's
+# three-launch branch without a hook; 5200 and 4000 blocks (5200 % 256 = 80, 4000 % 256 = 160), 7-8 cyclic-reduction
+# levels under the arrow solve with 4 and 3 right-hand-side batches; model 1: the 6-parameter double-sphere intrinsics
+SPLIT_RIGS = [(128, 1300, 4, 0), (171, 1000, 3, 0), (128, 1300, 4, 1)]
+
+
+@pytest.mark.parametrize("nf,npts,n_cams,model", SPLIT_RIGS)
+@pytest.mark.parametrize("lam", [1e-4, 1e-1])
+def test_free_intrinsics_split_border_against_fp64_reference(nf, npts, n_cams, model, lam):
+    """The border branch of C3/C4-sized free-intrinsics problems — intr_border_kernel with two waves per keyframe block,
+    intr_cam_dir_kernel and intr_cam_sch_kernel as three launches (enqueue_border, nf·nc ≥ 512) — reached by size alone,
+    against the fp64 reference (gn_reference.linearize_intrinsics / schur_step_intrinsics) with the comparisons and
+    tolerances of test_free_intrinsics_reduced_system_and_step.
+    Measured (MI355X), the worst of the six cases: cost 1.8e-8, S 5.5e-8, g 3.8e-8, pose + intrinsics
+    step 2.2e-6, δρ 7.9e-6, model decrease 7.5e-9 (λ = 1e-4; at λ = 1e-1 the steps are within 3.4e-8 / 2.1e-7)."""
+    pb, state, lin = _intrinsics_rig_reference(nf, npts, 61 + n_cams + model, n_cams, model)
+    assert pb.n_frames * pb.intrinsics.shape[0] >= 512  # the three-launch branch
+    assert pb.n_blocks % 256 in (80, 160)
+    _check_free_intrinsics_step(f"split border ({nf}, {npts}, {n_cams}) model {model}", pb, state, lam, lin)
+
+
+@pytest.mark.parametrize("nf,npts,n_cams", [(23, 260, 1), (23, 260, 2), (23, 260, 3), (23, 260, 4), (128, 1300, 4),
+                                            (23, 2600, 1), (23, 2600, 2)])
+def test_split_and_fused_border_agree(nf, npts, n_cams, monkeypatch):
+    """enqueue_border's two branches on the same problem (PBA_TEST_BORDER = fused | split, test build): one launch with
+    four waves per keyframe block against three launches with two.  The same fp64 terms added in another lane order, so
+    not bit-identical; held to the bound of test_arrow_and_front_solvers_agree for a differently ordered fp64
+    computation of the same step, 1e-8 relative.
+    Measured (MI355X): bit-identical (0.0) on the 260-point rigs and at (128, 1300, 4) — every
+    keyframe's lists there hold fewer than 64 entries, all taken by the first wave's lanes under either kpw; the
+    2600-point rigs (hundreds of entries per keyframe list, so every one of the two or four waves of a keyframe adds
+    entries) are the cases where the lane order differs: pose step 3.7e-15 / 7.0e-15, δρ 3.8e-15 / 1.7e-15, model decrease 1.3e-16 / 0, intrinsics step
+    0 (one and two cameras)."""
+    if (nf, npts, n_cams) in ((128, 1300, 4), (23, 2600, 2)):
+        pb, state, _ = _intrinsics_rig_reference(nf, npts, 61 + n_cams, n_cams, 0)
+    else:
+        pb, state = _intrinsics_rig(nf, npts, 51 + n_cams, n_cams)
+    out = {}
+    for branch in ("fused", "split"):
+        monkeypatch.setenv("PBA_TEST_BORDER", branch)
+        out[branch] = _free_intrinsics_step(pb, state, 1e-3, E.TEST_LIB_PATH)
+    _assert_same_step(f"border split vs fused ({nf}, {npts}, {n_cams})", out["split"], out["fused"], 1e-8)
+
+
+@pytest.mark.parametrize("lam", [1e-4, 1e-1])
+def test_free_intrinsics_long_keyframe_lists_against_fp64_reference(lam):
+    """Keyframe lists longer than one wave takes: 23 keyframes × 2600 points × 2 cameras gives a keyframe ≈ 550 hosted and
+    ≈ 550 targeting blocks, hundreds of entries per (camera, keyframe) list, so all four waves of a keyframe block (kpw =
+    4, the one-launch branch) add entries
+    and their sums are added in order through LDS (border_keyframes, sub ≥ 1) — on the 260-point rigs and at the
+    split-border sizes above only the first wave has any.  ≈ 137 points per host: two Schur chunks per host.  Against
+    the fp64 reference with the tolerances of test_free_intrinsics_reduced_system_and_step.
+    Measured (MI355X): cost 1.7e-8, S 3.8e-8, g 2.6e-8, step 1.0e-6, δρ 2.7e-6, model 1.1e-8."""
+    pb, state, lin = _intrinsics_rig_reference(23, 2600, 63, 2)
+    assert np.bincount(pb.point_host).min() * 4 > 256  # every hosting keyframe's block list exceeds 4 waves' lanes
+    _check_free_intrinsics_step("long keyframe lists (23, 2600, 2)", pb, state, lam, lin)
+
+
+def _long_point_problem(seed):
+    """_intrinsics_rig(23, 260, seed, 2) with 66 further observations of one point by its targets host + 1 … host + 4
+    (each its own block with its own observation noise): a point of 70 blocks while the keyframe band stays 4."""
+    pb, state = _intrinsics_rig(23, 260, seed, 2)
+    rng = np.random.default_rng(seed + 1000)
+    p = int(np.nonzero(pb.point_host == 9)[0][0])
+    h = int(pb.point_host[p])
+    tg = (h + 1 + np.arange(66) % 4).astype(np.int32)
+    Th, Tt = pb.poses_gt[h], pb.poses_gt[tg]
+    b = synth.unproject(pb.model, pb.intrinsics[pb.frame_cam[h]], pb.u_ref[p:p + 1])
+    pw = synth.quat_to_rot(Th[:4]) @ (b[0] / pb.rho_gt[p]) + Th[4:]
+    pt = (np.swapaxes(synth.quat_to_rot(Tt[:, :4]), -1, -2) @ (pw - Tt[:, 4:])[..., None])[..., 0]
+    assert (pt[:, 2] > 0.5).all()
+    uo = synth.project(pb.model, pb.intrinsics[pb.frame_cam[tg]], pt) + rng.normal(0, 0.3, (66, 2))
+    pb = synth.Problem(**{**pb.__dict__, "block_point": np.concatenate([pb.block_point, np.full(66, p, np.int32)]),
+                          "block_target": np.concatenate([pb.block_target, tg]),
+                          "u_obs": np.concatenate([pb.u_obs, uo])})
+    return pb, state
+
+
+@pytest.mark.parametrize("lam", [1e-4, 1e-1])
+def test_free_intrinsics_point_of_seventy_blocks_against_fp64_reference(lam):
+    """A point with more than 64 blocks, without a hook: gn_prepare gives up the point-aligned waves (ir_waves = 0), so
+    intr_rows_kernel runs its 64-block waves — 1106 blocks, 1106 % 256 = 82: the last workgroup's last two waves lie
+    wholly past the end and return — and intr_pw_kernel forms the points' sums; the keyframe border walks the point's
+    blocks (ib_pblk = −2: ~17 blocks of the point target each of its four keyframes).  The band stays 4 (the arrow
+    solve).  Against the fp64 reference, which sums per block, with the tolerances of
+    test_free_intrinsics_reduced_system_and_step.
+    Measured (MI355X): cost 1.5e-8, S 3.5e-8, g 2.7e-8, step 8.9e-7, δρ 2.5e-6, model 4.8e-9."""
+    key = ("long point", 47)
+    if key not in _INTR_REF:
+        pb, state = _long_point_problem(47)
+        _INTR_REF[key] = (pb, state, GR.linearize_intrinsics(pb, pb.poses, pb.rho, state, 1.0, (0, 1)))
+    pb, state, lin = _INTR_REF[key]
+    assert pb.n_blocks == 1106 and 1 <= pb.n_blocks % 256 <= 192  # a wave wholly past the end
+    assert np.bincount(pb.block_point).max() == 70  # > 64: no point-aligned waves
+    assert np.abs(pb.block_target - pb.point_host[pb.block_point]).max() == 4  # the band
+    _check_free_intrinsics_step("70-block point", pb, state, lam, lin)
+
+
+@pytest.mark.parametrize("lam", [1e-4, 1e-1])
+def test_free_intrinsics_five_cameras_against_fp64_reference(lam):
+    """Five cameras: more than the arrow solve takes (kArrowMaxNc = 4), so the skyline front solver gets the 10-row
+    border; 6·nf + 12·5 system rows (asserted in the shared check).  Against the fp64 reference with the tolerances of
+    test_free_intrinsics_reduced_system_and_step.
+    Measured (MI355X): cost 1.8e-8, S 4.9e-8, g 2.1e-8, step 1.3e-6, δρ 4.3e-6, model 6.9e-9."""
+    pb, state, lin = _intrinsics_rig_reference(40, 400, 73, 5)
+    assert pb.intrinsics.shape[0] == 5 and np.bincount(pb.frame_cam[pb.block_target], minlength=5).all()
+    _check_free_intrinsics_step("five cameras (40, 400, 5)", pb, state, lam, lin)
+
+
+def test_five_cameras_point_sums_in_rows_match_separate_kernel(monkeypatch):
+    """Five cameras through intr_pw_kernel (PBA_TEST_ROW_WAVES64, test build): its second group of four cameras holds
+    one camera.  The same sums in the same block order as intr_rows_kernel's point-aligned waves: the step to 1e-12, as
+    test_point_sums_in_rows_match_separate_kernel.  Measured (MI355X): bit-identical (0.0)."""
+    pb, state, _ = _intrinsics_rig_reference(40, 400, 73, 5)
+    out = {}
+    for path in ("fused", "separate"):
+        if path == "separate":
+            monkeypatch.setenv("PBA_TEST_ROW_WAVES64", "1")
+        out[path] = _free_intrinsics_step(pb, state, 1e-3, E.TEST_LIB_PATH)
+    _assert_same_step("five cameras, separate point sums", out["separate"], out["fused"], 1e-12)
 
 
 @pytest.mark.parametrize("force_degen", [False, True])
