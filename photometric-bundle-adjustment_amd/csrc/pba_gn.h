@@ -1,0 +1,65 @@
+// pba_gn.h — what the Gauss-Newton units share: pba_gn.hip (elimination, assembly, solve, update, LM loops) and
+// pba_gn_linearize.hip (the linearisation).  The pipeline of a trial is described in pba_gn.hip.
+#pragma once
+
+#include "pba_internal.h"
+
+namespace pba {
+namespace detail {
+
+typedef double v4f64 __attribute__((ext_vector_type(4)));
+
+constexpr int kPd = 8;            // point data per GN block: [H_ρρ, g_ρ, W_t(6)] (blk_schur)
+constexpr int SLOT_LIN_BASE = 42;  // H_hh(36) + g_h(6)
+constexpr int SLOT_LIN_T = 78;     // H_ht(36) + H_tt(36) + g_t(6)
+
+// At most this many targets per linearise chunk (gn_prepare cuts chunks there): a wave's blocks then hold ≤ 4 target
+// runs, so its per-run product sets (fp64) fit the LDS the fp32 ones took for 8.
+constexpr int kChunkTargets = 4;
+
+// LM decision record kept on the device by the single-GPU loop (lm_decide_kernel).
+// The trial's outcome, then the trust-region state the next trial runs with (λ = 1/radius, read by the kernels), the
+// done flag (every later kernel of the solve returns at once: 1 function tolerance, 2 consecutive invalid steps,
+// 3 parameter tolerance, 4 gradient tolerance, 5 minimum trust region radius; lm_decide), the index of the
+// linearisation buffer set holding the current state's normal-equation pieces (flipped on acceptance), and Ceres'
+// bookkeeping: the current state's valid blocks, x_norm (−1 until the first accepted step), consecutive invalid steps,
+// and the trial's step and gradient norms.
+enum : int {
+  kLmCost = 0, kLmCostNew = 1, kLmModel = 2, kLmRel = 3, kLmAccept = 4, kLmStatus = 5, kLmConverged = 6,
+  kLmLambda = 7, kLmRadius = 8, kLmFactor = 9, kLmDone = 10, kLmSet = 11, kLmValid = 12, kLmXNorm = 13,
+  kLmInvalid = 14, kLmStepNorm = 15, kLmGradNorm = 16, kLmDesync = 17, kLmFields = 18
+};
+
+// The kernels always get a record: the device loop's, or — host-driven steps — GnData::lm_idle (not done, set 0, λ NaN
+// = use the kernel's λ argument).  They read it with their first loads, never behind a branch of its own (a gate
+// read before anything else cost the linearisation ~8 µs of serialised scalar round trips).
+struct LmView {
+  double done, set, lambda, accept;
+};
+__device__ __forceinline__ LmView lm_view(const double* lm) {
+  return LmView{lm[kLmDone], lm[kLmSet], lm[kLmLambda], lm[kLmAccept]};
+}
+
+struct LinArgs {
+  const int4* lin_rec;      // chunk slot → {block, point, pair | local target slot << 24, GN position (blk_schur index)}
+  double* blk_schur1;       // the second buffer set (device LM loop: the candidate's linearisation goes to the spare)
+  double* part_lin1;
+  double* wg_red;           // per-chunk (Σ cost, Σ valid) slots, or nullptr
+  const int4* chunk_desc;   // first linearise position, count, n_targets, partial offset (slots)
+  double* blk_schur;
+  double* part_lin;
+  int n_chunks;
+  const double* lm;         // LM record: skip when the solve is done; spare: write the set the record does not hold
+  bool spare;
+  int* lin_set;             // or nullptr: the set written (workgroup 0 stores it, and clears degen[set])
+  int* degen;
+  double* pair_rt;          // per pair [R_th(9), t_th(3)] of the linearisation (set 0 / set 1): schur_chunk forms
+  double* pair_rt1;         // W_h = −W_t·Ad from them
+};
+
+// pba_gn_linearize.hip: the linearisation's launch for the engine's camera model (and interpolator)
+void launch_linearize_photometric(pba_engine* e, const KernelArgs& ka, const LinArgs& la);
+void launch_linearize_geometric(pba_engine* e, const KernelArgs& ka, const LinArgs& la);
+
+}  // namespace detail
+}  // namespace pba

@@ -1,5 +1,5 @@
 // pba_internal.h — engine state, kernel argument blocks and the per-row residual/Jacobian arithmetic
-// shared by the Ceres-mode kernels (pba_engine.hip) and the Gauss-Newton kernels (pba_gn.hip).
+// shared by the Ceres-mode kernels (pba_engine.hip) and the Gauss-Newton kernels (pba_gn.hip, pba_gn_linearize.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -806,7 +806,7 @@ struct GnData {
   DevBuf<PairRec> pairs_new;
   bool pairs_new_fresh = false;  // pairs_new formed by the last update_kernel (its candidate state)
   PinnedBuf<double> red_h;
-  DevBuf<double> lm;         // LM decision record of the single-GPU loop (pba_gn.hip: kLm*)
+  DevBuf<double> lm;         // LM decision record of the single-GPU loop (pba_gn.h: kLm*)
   DevBuf<double> lm_init;    // the solve's initial cost and valid blocks (lm_init_kernel)
   DevBuf<double> lm_idle;    // the record host-driven steps pass to the kernels (not done, set 0, λ from the argument)
   PinnedBuf<double> lm_h;    // its host copy (+ sequence number), host-coherent, written by lm_decide_kernel
