@@ -1,5 +1,6 @@
-// pba_gn.h — what the Gauss-Newton units share: pba_gn.hip (elimination, assembly, solve, update, LM loops) and
-// pba_gn_linearize.hip (the linearisation).  The pipeline of a trial is described in pba_gn.hip.
+// pba_gn.h — what the Gauss-Newton units share: pba_gn.hip (elimination, assembly, update, LM loops),
+// pba_gn_linearize.hip (the linearisation) and pba_gn_solve_cr.hip (v4f64; the solvers' own interface is pba_gn_solve.h).
+// The pipeline of a trial is described in pba_gn.hip.
 #pragma once
 
 #include "pba_internal.h"

@@ -13,7 +13,9 @@
 //                          rows for constant frames; writes cyclic reduction's level 0 directly.
 //   cr_level_wave_kernel   block (parallel) cyclic reduction, one launch per level (band ≤ 8); band_solve_kernel
 //                          (band ≤ 16); front_solve_kernel (any profile: loop closures, the free-intrinsics border —
-//                          the active front in LDS) or skyline_solve_kernel (global memory).
+//                          the active front in LDS) or skyline_solve_kernel (global memory).  Cyclic reduction, the
+//                          arrow solve of free intrinsics and the solver choice: pba_gn_solve_cr.hip; the band, front
+//                          and skyline Cholesky: pba_gn_solve_sky.hip; what this unit calls of them: pba_gn_solve.h.
 //   update_kernel          T ← T·exp(δ) (Sophus SE3::exp, fp64), δρ = −(g_ρ + Σ W_aᵀ δ_a)/H'_ρρ, the LM model
 //                          decrease ½(λ δᵀDδ − gᵀδ) and the candidate pair table, in one launch.
 //   linearize_adj_kernel   at the candidate (photometric, ≤ 32 px): rows of 8 lanes per block, the target's 8-column
@@ -42,7 +44,7 @@
 #include <vector>
 
 #include "pba_gn.h"
-
+#include "pba_gn_solve.h"
 
 using namespace pba;
 using namespace pba::detail;
@@ -778,1572 +780,6 @@ __global__ void import_sky_kernel(const ImportSkyArgs a, double lambda, const do
   a.g_dir[u] = fi || pad ? 0.0 : tail[6 + r];
   a.Ddiag[u] = fi ? 0.0 : (pad ? 1.0 : fmin(fmax(tail[12 + r], 1e-6), 1e32));
   if (r == 0) a.fixed[i] = fi ? 1 : 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// skyline_solve_kernel: S δ = −g, S = LLᵀ in place (block skyline, right-looking), one workgroup
-// ------------------------------------------------------------------------------------------------
-// chol6 / inv_lower6: the 6×6 diagonal block's Cholesky factor and its inverse, on register arrays (fully unrolled)
-__device__ __forceinline__ bool chol6_reg(const double (&A)[36], double (&L)[36]) {
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < 36; ++i) L[i] = 0.0;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double s = A[j * 6 + j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) s -= L[j * 6 + k] * L[j * 6 + k];
-    ok = ok && s > 0.0;
-    const double ljj = sqrt(fmax(s, 1e-300));
-    L[j * 6 + j] = ljj;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double t = A[i * 6 + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) t -= L[i * 6 + k] * L[j * 6 + k];
-      L[i * 6 + j] = t / ljj;
-    }
-  }
-  return ok;
-}
-__device__ __forceinline__ void inv_lower6_reg(const double (&L)[36], double (&Li)[36]) {
-#pragma unroll
-  for (int i = 0; i < 36; ++i) Li[i] = 0.0;
-#pragma unroll
-  for (int c = 0; c < 6; ++c) {
-    Li[c * 6 + c] = 1.0 / L[c * 6 + c];
-#pragma unroll
-    for (int r = c + 1; r < 6; ++r) {
-      double s = 0.0;
-#pragma unroll
-      for (int k = c; k < r; ++k) s += L[r * 6 + k] * Li[k * 6 + c];
-      Li[r * 6 + c] = -s / L[r * 6 + r];
-    }
-  }
-}
-
-struct SolveArgs {
-  double* S;
-  const int* first;
-  const int* row;
-  const int* last;
-  const double* g;
-  double* Linv;
-  double* x;
-  int* status;
-  int N;
-  const int* cptr;   // column k's profile rows crows[cptr[k] … cptr[k+1]) (every i > k with first(i) ≤ k, in order)
-  const int* crows;
-};
-
-__device__ __forceinline__ long long sky_off(const SolveArgs& a, int i, int j) {  // block (i, j), j ≥ first(i)
-  return ((long long)a.row[i] + (j - a.first[i])) * 36;
-}
-
-__global__ __launch_bounds__(256) void skyline_solve_kernel(const SolveArgs a) {
-  __shared__ double sA[36], sL[36], sLi[36];
-  __shared__ int s_fail;
-  const int tid = threadIdx.x;
-  if (tid == 0) s_fail = 0;
-  for (int k = 0; k < a.N; ++k) {
-    const long long okk = sky_off(a, k, k);
-    if (tid < 36) sA[tid] = a.S[okk + tid];
-    __syncthreads();
-    if (tid == 0) {  // in registers: the LDS-pointer forms' dependent LDS round trips were most of a column's time
-      double A[36], L[36], Li[36];
-#pragma unroll
-      for (int q = 0; q < 36; ++q) A[q] = sA[q];
-      if (!chol6_reg(A, L)) {
-        s_fail = k + 1;
-      } else {
-        inv_lower6_reg(L, Li);
-#pragma unroll
-        for (int q = 0; q < 36; ++q) {
-          sL[q] = L[q];
-          sLi[q] = Li[q];
-        }
-      }
-    }
-    __syncthreads();
-    if (s_fail) {
-      if (tid == 0) *a.status = s_fail;
-      return;
-    }
-    if (tid < 36) {
-      a.S[okk + tid] = sL[tid];
-      a.Linv[(long long)k * 36 + tid] = sLi[tid];
-    }
-    // column k's profile rows: the band below the diagonal and, with free intrinsics, the dense border rows — walking
-    // (k, last(k)] instead enumerated every row pair up to the border, O(N²) per column (C3 with free intrinsics: 0.7 s
-    // per solve)
-    const int c0 = a.cptr[k], na = a.cptr[k + 1] - c0;
-    const int* rows = a.crows + c0;
-    // column panel L_ik = A_ik · L_kk⁻ᵀ, 7 blocks per pass (read all, barrier, write)
-    for (int i0 = 0; i0 < na; i0 += 7) {
-      double val = 0.0;
-      long long dst = -1;
-      const int li = i0 + tid / 36;
-      if (tid < 252 && li < na) {
-        const int i = rows[li], e = tid % 36, r = e / 6, c = e % 6;
-        const long long o = sky_off(a, i, k);
-        for (int m = 0; m <= c; ++m) val += a.S[o + r * 6 + m] * sLi[c * 6 + m];
-        dst = o + e;
-      }
-      __syncthreads();
-      if (dst >= 0) a.S[dst] = val;
-      __threadfence_block();
-      __syncthreads();
-    }
-    // trailing update A_ij −= L_ik L_jkᵀ over the pairs of the column's rows (i ≥ j)
-    const int npairs = na * (na + 1) / 2;
-    for (int idx = tid; idx < npairs * 36; idx += 256) {
-      const int pidx = idx / 36, e = idx % 36, r = e / 6, c = e % 6;
-      int ii = 0;  // decode lower-triangular pair index → (ii ≥ jj)
-      while ((ii + 1) * (ii + 2) / 2 <= pidx) ++ii;
-      const int jj = pidx - ii * (ii + 1) / 2;
-      const int i = rows[ii], j = rows[jj];
-      const long long oi = sky_off(a, i, k), oj = sky_off(a, j, k);
-      double s = 0.0;
-      for (int m = 0; m < 6; ++m) s += a.S[oi + r * 6 + m] * a.S[oj + c * 6 + m];
-      a.S[sky_off(a, i, j) + e] -= s;
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  // forward substitution L y = −g (y in x)
-  for (int t = tid; t < 6 * a.N; t += 256) a.x[t] = -a.g[t];
-  __threadfence_block();
-  __syncthreads();
-  for (int k = 0; k < a.N; ++k) {
-    __shared__ double yk[6];
-    if (tid < 6) {
-      double s = 0.0;
-      for (int m = 0; m <= tid; ++m) s += a.Linv[(long long)k * 36 + tid * 6 + m] * a.x[6 * k + m];
-      yk[tid] = s;
-    }
-    __syncthreads();
-    if (tid < 6) a.x[6 * k + tid] = yk[tid];
-    const int c0 = a.cptr[k], na = a.cptr[k + 1] - c0;
-    for (int idx = tid; idx < na * 6; idx += 256) {
-      const int i = a.crows[c0 + idx / 6], r = idx % 6;
-      const long long o = sky_off(a, i, k);
-      double s = 0.0;
-      for (int m = 0; m < 6; ++m) s += a.S[o + r * 6 + m] * yk[m];
-      a.x[6 * i + r] -= s;
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  // back substitution Lᵀ x = y
-  for (int k = a.N - 1; k >= 0; --k) {
-    __shared__ double tk[6];
-    if (tid < 6) {
-      double s = a.x[6 * k + tid];
-      for (int q = a.cptr[k]; q < a.cptr[k + 1]; ++q) {
-        const int i = a.crows[q];
-        const long long o = sky_off(a, i, k);
-        for (int m = 0; m < 6; ++m) s -= a.S[o + m * 6 + tid] * a.x[6 * i + m];
-      }
-      tk[tid] = s;
-    }
-    __syncthreads();
-    if (tid < 6) {
-      double s = 0.0;
-      for (int m = tid; m < 6; ++m) s += a.Linv[(long long)k * 36 + m * 6 + tid] * tk[m];
-      a.x[6 * k + tid] = s;
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  if (tid == 0) *a.status = 0;
-}
-
-// rsqrt_nr (pba_device.h): hardware v_rsq_f64 seed + two Newton steps — the pivot is on the solver's
-// serial critical path; this is ~3x shorter than sqrt() + division.
-__device__ inline bool chol6_rcp(double* A, double* invd) {  // in place, lower; returns reciprocal pivots
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double s = A[j * 6 + j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) s -= A[j * 6 + k] * A[j * 6 + k];
-    if (!(s > 0.0)) return false;
-    const double il = rsqrt_nr(s), l = s * il;
-    A[j * 6 + j] = l;
-    invd[j] = il;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double t = A[i * 6 + j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) t -= A[i * 6 + k] * A[j * 6 + k];
-      A[i * 6 + j] = t * il;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = i + 1; j < 6; ++j) A[i * 6 + j] = 0.0;
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------
-// front_solve_kernel: the same factorisation and solve with the ACTIVE FRONT in LDS (one workgroup)
-// ------------------------------------------------------------------------------------------------
-// Right-looking block Cholesky touches, at column k, only the blocks among {k} ∪ rows(k), rows(k) = {i > k : first(i) ≤ k}
-// — the front.  It moves by one row per column: k leaves, the rows with first(i) = k + 1 enter with their blocks fresh
-// from S (no earlier column touched them).  gn_prepare gives every row a static LDS slot (a row admitted for column k + 1
-// never takes a slot in use at column k) and writes per column a record: the slots, row indices and factor-block
-// indices of rows(k), and the fresh blocks of the next column's admissions (source skyline block → front position
-// slot_hi·F + slot_lo) — build_front_plan; a multi-GPU free-intrinsics solve has a plan of its own for the summed
-// profile (ensure_dist_sky).  skyline_solve_kernel walks the same factorisation through global memory, a dependent L2
-// round trip per phase (≈ 9 µs per column); here the front, the forward vector and the records live in LDS and the
-// next column's fresh blocks and record are loaded while this column is factored.  Free intrinsics make the profile a
-// band plus 2·nc dense border rows: F = K + 1 + 2nc slots (C3/C4: 7).
-// Every lane issues its share of the global loads of the record two columns ahead and of the next column's fresh
-// blocks (backward: its staged factor blocks) at a column's start and stores them to LDS at its end.  (A dedicated
-// loader wave measured slower: the compiler's conservative waits then stalled that wave at the barriers.)
-// Forward (2 barriers per column): 6·|rows(k)| lanes form L_ik = A_ik L_kk⁻ᵀ row by row (to LDS, to L, v_i −= L_ik y_k);
-// then the trailing pairs A_ij −= L_ik L_jkᵀ while one lane finishes and factors the next diagonal block (look-ahead:
-// L_kk, reciprocal pivots and y_k = L_kk⁻¹ v_k were formed during column k − 1).
-// Backward (2 barriers per column): 6·|rows(k)| lanes form the products L_ikᵀ x_i, six lanes add them in order and one
-// solves x_k = L_kk⁻ᵀ (y_k − Σ_i L_ikᵀ x_i).
-constexpr int kFrontHdr = 3;
-struct FrontArgs {
-  const double* S;      // the assembled skyline system
-  const double* g;
-  double* L;            // the factor's off-diagonal blocks (skyline layout)
-  double* lrec;         // per column: L_kk | 1/pivots | y_k
-  const int* rec;       // per column: kFrontHdr + 3·fm + 2·mf ints
-  const int2* init;     // the rows of column 0's front: (source block, front position)
-  double* x;
-  int* status;
-  int N, F, fm, mf, R, n_init;
-};
-constexpr int kFrontPf = 4;  // doubles per lane per column: fresh blocks (mf·36) / staged blocks (fm·36 + 48)
-constexpr int kFrontPr = 1;  // record ints per lane (R ≤ 256)
-
-__global__ __launch_bounds__(256) void front_solve_kernel(const FrontArgs a) {
-  extern __shared__ double front_lds[];
-  const int tid = threadIdx.x, N = a.N, F = a.F, fm = a.fm, mf = a.mf, R = a.R;
-  const int SB = fm * 36 + 48, ld = tid;
-  double* fr = front_lds;                                // F·F blocks: block (i ≥ j) at slot_i·F + slot_j
-  double* ys = fr + (size_t)F * F * 36;                  // v → y → x, 6 per row
-  double* stg = ys + 6 * N;                              // backward: 2 × SB
-  int* recb = reinterpret_cast<int*>(stg + 2 * SB);      // 3 × R: records k, k + 1, k + 2 (backward: k, k − 1, k − 2)
-  int* pairs = recb + 3 * R;                             // lower-triangle pair p → (ii << 16) | jj
-  __shared__ double sL[2][36], sd[2][6], sy[2][6], sp[6 * 32];  // the diagonal factor of columns k, k + 1
-  __shared__ double sDn[36];                                       // column k + 1's diagonal block (look-ahead)
-  __shared__ int s_fail;
-#ifdef PBA_FRONT_STAMPS  // timing variant: per-phase wall-clock sums of lanes 0, 64 and 192, written over x[0 … 29]
-  unsigned long long fts[10] = {}, ft0 = 0;
-#define FRONT_STAMP(i) { const unsigned long long t_ = wall_clock64(); if ((i) > 0) fts[(i) - 1] += t_ - ft0; ft0 = t_; }
-#else
-#define FRONT_STAMP(i)
-#endif
-  // the prefetch loads: unconditional (clamped addresses; the stores are guarded) — under a branch, the compiler waited
-  // for every load in flight at the first use of any
-  auto load_rec = [&](int k, int (&regs)[kFrontPr]) {
-#pragma unroll
-    for (int q = 0; q < kFrontPr; ++q)
-      regs[q] = a.rec[(long long)min(max(k, 0), N - 1) * R + min(ld + 256 * q, R - 1)];
-  };
-  auto store_rec = [&](int k, const int (&regs)[kFrontPr]) {
-#pragma unroll
-    for (int q = 0; q < kFrontPr; ++q)
-      if (ld + 256 * q < R) recb[(k % 3) * R + ld + 256 * q] = regs[q];
-  };
-  auto load_fresh = [&](const int* rk, double (&regs)[kFrontPf]) {  // the blocks column k admits for column k + 1
-    const int nfr = rk[2];
-    const int* fsrc = rk + kFrontHdr + 3 * fm;
-#pragma unroll
-    for (int q = 0; q < kFrontPf; ++q) {
-      const int idx = min(ld + 256 * q, max(nfr * 36 - 1, 0));
-      regs[q] = a.S[(long long)(nfr ? fsrc[idx / 36] : 0) * 36 + idx % 36];
-    }
-  };
-  if (tid == 0) s_fail = 0;
-  for (int t = tid; t < 6 * N; t += 256) ys[t] = -a.g[t];
-  for (int t = tid; t < a.n_init * 36; t += 256) {
-    const int2 q = a.init[t / 36];
-    fr[(long long)q.y * 36 + t % 36] = a.S[(long long)q.x * 36 + t % 36];
-  }
-  for (int t = tid; t < 2 * R; t += 256)
-    if (t / R < N) recb[t] = a.rec[t];
-  for (int p = tid; p < fm * (fm + 1) / 2; p += 256) {
-    int ii = 0;
-    while ((ii + 1) * (ii + 2) / 2 <= p) ++ii;
-    pairs[p] = (ii << 16) | (p - ii * (ii + 1) / 2);
-  }
-  __syncthreads();
-
-  // the 6×6 factor of a diagonal block, y = L⁻¹ v, into buffer set q (one lane); false: not positive definite
-  auto factor = [&](const double (&D)[36], int col, int q) -> bool {
-    double A[36], d[6];
-#pragma unroll
-    for (int e = 0; e < 36; ++e) A[e] = D[e];
-    if (!chol6_rcp(A, d)) return false;
-    double b[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) b[r] = ys[6 * col + r];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {  // y_col = L⁻¹ v_col
-      double t = b[c];
-#pragma unroll
-      for (int m = 0; m < c; ++m) t -= A[c * 6 + m] * b[m];
-      b[c] = t * d[c];
-    }
-#pragma unroll
-    for (int e = 0; e < 36; ++e) sL[q][e] = A[e];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      sd[q][r] = d[r];
-      sy[q][r] = b[r];
-      ys[6 * col + r] = b[r];
-    }
-    return true;
-  };
-  auto factor_lds = [&](int col, int slot, int q) {  // column col's diagonal block as it stands in the front
-    double D[36];
-    const double* Dk = fr + (long long)(slot * F + slot) * 36;
-#pragma unroll
-    for (int e = 0; e < 36; ++e) D[e] = Dk[e];
-    if (!factor(D, col, q)) s_fail = col + 1;
-  };
-  if (N > 0 && tid == 0) factor_lds(0, recb[0], 0);
-  __syncthreads();
-  if (s_fail) {
-    if (tid == 0) *a.status = s_fail;
-    return;
-  }
-
-  // One column, LOOK-AHEAD: its diagonal block was factored during the previous column (buffer set k & 1).  Panel,
-  // then — while lanes 0-191 run the trailing update — lane 192 forms column k + 1's diagonal block (its last update,
-  // −L_{k+1,k} L_{k+1,k}ᵀ, when k + 1 is the column's first row) and factors it: the 6×6 factor's serial chain is off
-  // the critical path.  A column k + 1 outside rows(k) (admitted fresh at k + 1) is factored after the barrier.
-  // cur holds the column's admissions (loaded during the previous column), nxt receives the next column's — two
-  // columns per pass with the arrays swapped (no register copies).
-  auto column = [&](int k, double (&cur)[kFrontPf], double (&nxt)[kFrontPf]) -> bool {
-    const int* rk = recb + (k % 3) * R;
-    const int sk = rk[0], na = rk[1], nfr = rk[2], q = k & 1;
-    const int* slots = rk + kFrontHdr;
-    const int* rows = slots + fm;
-    const int* gbl = rows + fm;
-    const int* fdst = gbl + fm + mf;
-    FRONT_STAMP(0);
-    int pr[kFrontPr];
-    load_rec(k + 2, pr);  // before the fresh loads: waiting for it must not wait for them
-    if (k + 1 < N) load_fresh(recb + ((k + 1) % 3) * R, nxt);
-    FRONT_STAMP(1);
-    FRONT_STAMP(2);
-    if (tid < na * 6) {  // panel row r of L_ik = A_ik L_kk⁻ᵀ; v_i −= L_ik y_k
-      const int li = tid / 6, r = tid % 6;
-      double* A = fr + (long long)(slots[li] * F + sk) * 36 + r * 6;
-      double X[6];
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        double t = A[c];
-#pragma unroll
-        for (int m = 0; m < c; ++m) t -= X[m] * sL[q][c * 6 + m];
-        X[c] = t * sd[q][c];
-      }
-      double* Lg = a.L + (long long)gbl[li] * 36 + r * 6;
-      double dv = 0.0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        A[c] = X[c];
-        Lg[c] = X[c];
-        dv += X[c] * sy[q][c];
-      }
-      ys[6 * rows[li] + r] -= dv;
-    } else if (tid >= 192 && tid < 240) {
-      const int e = tid - 192;
-      a.lrec[(long long)k * 48 + e] = e < 36 ? sL[q][e] : (e < 42 ? sd[q][e - 36] : sy[q][e - 42]);
-    }
-    FRONT_STAMP(3);
-    __syncthreads();
-    FRONT_STAMP(4);
-    const bool ahead = k + 1 < N && na > 0 && rows[0] == k + 1;  // (uniform)
-    const int np = na * (na + 1) / 2;  // trailing A_ij −= L_ik L_jkᵀ (i ≥ j in rows(k)); pair 0 = (k+1, k+1) if ahead
-    if (tid < 192) {  // four items per lane in flight: their dependent LDS rounds (pair → slots → rows → element) overlap
-      constexpr int TR = 4;
-      const int i0 = ahead ? 36 : 0, ne = np * 36;
-      for (int base = i0 + tid; base < ne; base += 192 * TR) {
-        double acc[TR];
-        int dst[TR];
-#pragma unroll
-        for (int u = 0; u < TR; ++u) {
-          const int idx = min(base + 192 * u, ne - 1);
-          const int pq = pairs[idx / 36], e = idx % 36, r = e / 6, c = e % 6;
-          const int si = slots[pq >> 16], sj = slots[pq & 0xffff];
-          const double* Li = fr + (si * F + sk) * 36 + r * 6;
-          const double* Lj = fr + (sj * F + sk) * 36 + c * 6;
-          double t = 0.0;
-#pragma unroll
-          for (int m = 0; m < 6; ++m) t += Li[m] * Lj[m];
-          acc[u] = t;
-          dst[u] = (si * F + sj) * 36 + e;
-        }
-#pragma unroll
-        for (int u = 0; u < TR; ++u)
-          if (base + 192 * u < ne) fr[dst[u]] -= acc[u];
-      }
-    } else if (ahead) {  // wave 3: column k + 1's diagonal block, final (lane e: entry e), then lane 192 factors it
-      const int s1 = slots[0], e = tid - 192;
-      if (e < 36) {
-        const double* Li = fr + (long long)(s1 * F + sk) * 36 + (e / 6) * 6;
-        const double* Lj = fr + (long long)(s1 * F + sk) * 36 + (e % 6) * 6;
-        double acc = 0.0;
-#pragma unroll
-        for (int m = 0; m < 6; ++m) acc += Li[m] * Lj[m];
-        sDn[e] = fr[(long long)(s1 * F + s1) * 36 + e] - acc;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (e == 0) {
-        double D[36];
-#pragma unroll
-        for (int i = 0; i < 36; ++i) D[i] = sDn[i];
-        if (!factor(D, k + 1, q ^ 1)) s_fail = k + 2;
-      }
-    }
-#pragma unroll
-    for (int qq = 0; qq < kFrontPf; ++qq) {  // column k's admissions (slots unused at column k), the record of k + 2
-      const int idx = ld + 256 * qq;
-      if (idx < nfr * 36) fr[(long long)fdst[idx / 36] * 36 + idx % 36] = cur[qq];
-    }
-    if (k + 2 < N) store_rec(k + 2, pr);
-    FRONT_STAMP(5);
-    __syncthreads();
-    FRONT_STAMP(6);
-    if (k + 1 < N && !ahead) {  // column k + 1 entered the front fresh: factor it now
-      if (tid == 0) factor_lds(k + 1, recb[((k + 1) % 3) * R], q ^ 1);
-      __syncthreads();
-    }
-    if (s_fail) {
-      if (tid == 0) *a.status = s_fail;
-      return false;
-    }
-    return true;
-  };
-  double pf[kFrontPf], pfn[kFrontPf];
-  load_fresh(recb, pf);
-  for (int k = 0; k < N; k += 2) {
-    if (!column(k, pf, pfn)) return;
-    if (k + 1 < N && !column(k + 1, pfn, pf)) return;
-  }
-  __threadfence();
-  __syncthreads();
-
-  // backward: x_k = L_kk⁻ᵀ (y_k − Σ_i L_ikᵀ x_i); column k's blocks staged during column k + 1, loaded during k + 2
-  auto load_stage = [&](int k, const int* rk, double (&regs)[kFrontPf]) {
-    const int na = rk[1];
-    const int* gbl = rk + kFrontHdr + 2 * fm;
-#pragma unroll
-    for (int q = 0; q < kFrontPf; ++q) {  // unused stage entries hold any value
-      const int idx = ld + 256 * q;
-      const double* src = a.lrec;
-      if (k >= 0 && idx < na * 36) src = a.L + (long long)gbl[idx / 36] * 36 + idx % 36;
-      else if (k >= 0 && idx >= fm * 36 && idx < SB) src = a.lrec + (long long)k * 48 + idx - fm * 36;
-      regs[q] = *src;
-    }
-  };
-  auto store_stage = [&](int k, const double (&regs)[kFrontPf]) {
-#pragma unroll
-    for (int q = 0; q < kFrontPf; ++q)
-      if (ld + 256 * q < SB) stg[(k & 1) * SB + ld + 256 * q] = regs[q];
-  };
-  double pb[kFrontPf], pbn[kFrontPf];  // cur / nxt of bcolumn, swapped per column as the forward pass
-  for (int t = tid; t < 3 * R; t += 256) {
-    const int k = N - 1 - t / R;
-    if (k >= 0) recb[(k % 3) * R + t % R] = a.rec[(long long)k * R + t % R];
-  }
-  __syncthreads();
-  {
-    const int* rk = recb + ((N - 1) % 3) * R;
-    for (int t = tid; t < SB; t += 256) {
-      double v = 0.0;
-      if (t < rk[1] * 36) v = a.L[(long long)rk[kFrontHdr + 2 * fm + t / 36] * 36 + t % 36];
-      else if (t >= fm * 36) v = a.lrec[(long long)(N - 1) * 48 + t - fm * 36];
-      stg[((N - 1) & 1) * SB + t] = v;
-    }
-  }
-  load_stage(N - 2, recb + (((N - 2) % 3 + 3) % 3) * R, pb);
-  __syncthreads();
-  auto bcolumn = [&](int k, double (&cur)[kFrontPf], double (&nxt)[kFrontPf]) {
-    const int* rk = recb + (k % 3) * R;
-    const double* st = stg + (k & 1) * SB;
-    const int na = rk[1];
-    FRONT_STAMP(0);
-    int pr[kFrontPr];
-    load_rec(k - 3, pr);
-    load_stage(k - 2, recb + (((k - 2) % 3 + 3) % 3) * R, nxt);
-    if (tid < na * 6) {  // (L_ikᵀ x_i)_r
-      const int li = tid / 6, r = tid % 6;
-      const double* Lb = st + li * 36 + r;
-      const double* xi = ys + 6 * rk[kFrontHdr + fm + li];
-      double p = 0.0;
-#pragma unroll
-      for (int m = 0; m < 6; ++m) p += Lb[m * 6] * xi[m];
-      sp[tid] = p;
-    }
-    FRONT_STAMP(7);
-    __syncthreads();
-    FRONT_STAMP(8);
-    if (tid < 64) {  // lanes 0-5 add the products of entry r in order, lane 0 solves
-      double tr = 0.0;
-      if (tid < 6) {
-        tr = st[fm * 36 + 42 + tid];
-        for (int li = 0; li < na; ++li) tr -= sp[li * 6 + tid];
-      }
-      double t[6];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) t[r] = __shfl(tr, r, 64);
-      if (tid == 0) {
-#pragma unroll
-      for (int r = 5; r >= 0; --r) {  // L_kkᵀ x = t
-        double v = t[r];
-#pragma unroll
-        for (int m = r + 1; m < 6; ++m) v -= st[fm * 36 + m * 6 + r] * t[m];
-        t[r] = v * st[fm * 36 + 36 + r];
-      }
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        ys[6 * k + r] = t[r];
-        a.x[6 * k + r] = t[r];
-      }
-      }
-    }
-    if (k >= 1) store_stage(k - 1, cur);  // column k − 1's stage (not read at column k)
-    if (k >= 3) store_rec(k - 3, pr);     // the record of k − 3 (over record k)
-    FRONT_STAMP(9);
-    __syncthreads();
-    FRONT_STAMP(10);
-  };
-  for (int k = N - 1; k >= 0; k -= 2) {
-    bcolumn(k, pb, pbn);
-    if (k >= 1) bcolumn(k - 1, pbn, pb);
-  }
-  if (tid == 0) *a.status = 0;
-#ifdef PBA_FRONT_STAMPS
-  __syncthreads();
-  if (tid == 0 || tid == 64 || tid == 192)
-    for (int i = 0; i < 10; ++i) a.x[(tid == 0 ? 0 : (tid == 64 ? 10 : 20)) + i] = (double)fts[i];
-#endif
-#undef FRONT_STAMP
-}
-
-// ------------------------------------------------------------------------------------------------
-// band_solve_kernel<B>: the same factorisation when every block row satisfies first(i) ≥ i − B (the
-// structure of windowed/sequential BA — C3/C4 have B = 4).  The assembly also writes S in dense band
-// layout (block c of row i = column i − B + c), so the next block row's address needs no indirection.
-// The active window of the factor (block rows k..k+B) lives in LDS as a ring; block row k+B+2 is
-// prefetched into registers two steps ahead.  Per step: one lane factors the 6×6 diagonal block
-// (reciprocal pivots, no inverse), B·6 lanes solve the column panel L_ik = A_ik L_kk⁻ᵀ row by row, the
-// trailing triangle is updated in parallel, and forward substitution is fused in.  Finished rows of L and
-// the reciprocal pivots go to global memory for the backward pass, which prefetches one step ahead.
-// ------------------------------------------------------------------------------------------------
-struct BandArgs {
-  const double* Sband;  // N rows × ((B+1)·36 + 6): blocks of columns i−B..i, then g_i
-  double* Lcol;         // N column records × (B·36 + 48): L_(k+q),k for q = 1..B | L_kk | 1/pivots | y_k
-  double* x;            // the step δ_poses
-  int* status;
-  int N;
-};
-
-template <int B>
-__global__ __launch_bounds__(256) void band_solve_kernel(const BandArgs a) {
-  constexpr int W = B + 1;
-  constexpr int ROWF = W * 36;
-  constexpr int ROWG = ROWF + 6;
-  constexpr int COLF = B * 36 + 48;
-  constexpr int CH = B <= 8 ? 16 : 4;      // rows / column records per prefetch chunk
-  constexpr int STG = CH * COLF;           // ≥ CH·ROWG
-  constexpr int PCH = (STG + 255) / 256;
-  __shared__ double win[W * ROWG];         // ring of block rows k..k+B (slot i % W)
-  __shared__ double stage[2 * STG];        // double-buffered prefetch chunks
-  __shared__ double ring[W * 6];           // y (forward) / x (backward) of the last B+1 block rows
-  __shared__ double sd[6], sv[6];
-  __shared__ int s_fail;
-  const int tid = threadIdx.x, N = a.N;
-
-  // ---- forward: factor + fused forward substitution -------------------------------------------------
-  auto load_rows = [&](int r0, double* regs) {  // rows r0 .. r0+CH−1 (zero beyond N)
-#pragma unroll
-    for (int q = 0; q < PCH; ++q) {
-      const int idx = tid + q * 256;
-      const int i = r0 + idx / ROWG;
-      regs[q] = (idx < CH * ROWG && i < N) ? a.Sband[(long long)r0 * ROWG + idx] : 0.0;
-    }
-  };
-  auto put_stage = [&](int buf, const double* regs, int n) {
-#pragma unroll
-    for (int q = 0; q < PCH; ++q) {
-      const int idx = tid + q * 256;
-      if (idx < n) stage[buf * STG + idx] = regs[q];
-    }
-  };
-  if (tid == 0) s_fail = 0;
-  for (int idx = tid; idx < W * ROWG; idx += 256)
-    win[idx] = (idx / ROWG < N) ? a.Sband[idx] : 0.0;  // rows 0..B into slots 0..B
-  if (tid < W * 6) ring[tid] = 0.0;
-  double pf[PCH];
-  load_rows(W, pf);
-  put_stage(0, pf, CH * ROWG);
-  __syncthreads();
-
-  for (int k = 0; k < N; ++k) {
-    const int c = k / CH, o = k % CH;
-    double* rk = win + (k % W) * ROWG;
-    double* Lkk = rk + B * 36;
-    if (o == 0) load_rows(W + (c + 1) * CH, pf);  // next chunk, lands during the next CH steps
-    if (tid == 0) {
-      double A[36], d[6];
-#pragma unroll
-      for (int e = 0; e < 36; ++e) A[e] = Lkk[e];
-      if (!chol6_rcp(A, d)) {
-        s_fail = k + 1;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 36; ++e) Lkk[e] = A[e];
-#pragma unroll
-        for (int e = 0; e < 6; ++e) sd[e] = d[e];
-      }
-    } else if (tid >= 64 && tid < 70) {  // b_k = −g_k − Σ_j L_kj y_j   (L_kj final, y_j in the ring)
-      const int r = tid - 64;
-      double v = -rk[ROWF + r];
-#pragma unroll
-      for (int cc = 0; cc < B; ++cc) {
-        const int j = k - B + cc;
-        if (j < 0) continue;
-        const double* Lb = rk + cc * 36 + r * 6;
-        const double* yj = ring + (j % W) * 6;
-#pragma unroll
-        for (int m = 0; m < 6; ++m) v -= Lb[m] * yj[m];
-      }
-      sv[r] = v;
-    }
-    __syncthreads();
-    if (s_fail) {
-      if (tid == 0) *a.status = s_fail;
-      return;
-    }
-    const int nk = min(B, N - 1 - k);
-    double* rec = a.Lcol + (long long)k * COLF;
-    if (tid < nk * 6) {  // panel row r of L_ik = A_ik L_kk⁻ᵀ
-      const int ii = 1 + tid / 6, r = tid % 6;
-      double* A = win + ((k + ii) % W) * ROWG + (B - ii) * 36 + r * 6;
-      double X[6];
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) {
-        double t = A[cc];
-#pragma unroll
-        for (int m = 0; m < cc; ++m) t -= X[m] * Lkk[cc * 6 + m];
-        X[cc] = t * sd[cc];
-      }
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) A[cc] = X[cc];
-    } else if (tid >= 192 && tid < 228) {
-      rec[B * 36 + (tid - 192)] = Lkk[tid - 192];
-    } else if (tid >= 228 && tid < 234) {
-      rec[B * 36 + 36 + (tid - 228)] = sd[tid - 228];
-    } else if (tid == 255) {  // y_k = L_kk⁻¹ b_k
-      double L[36], bb[6], d[6];
-#pragma unroll
-      for (int e = 0; e < 36; ++e) L[e] = Lkk[e];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) { bb[r] = sv[r]; d[r] = sd[r]; }
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) {
-        double t = bb[cc];
-#pragma unroll
-        for (int m = 0; m < cc; ++m) t -= L[cc * 6 + m] * bb[m];
-        bb[cc] = t * d[cc];
-      }
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        ring[(k % W) * 6 + r] = bb[r];
-        rec[B * 36 + 42 + r] = bb[r];
-      }
-    }
-    __syncthreads();
-    // trailing update A_ij −= L_ik L_jkᵀ (k < j ≤ i ≤ k+nk); column k of L to the record
-    const int npairs = nk * (nk + 1) / 2;
-    for (int idx = tid; idx < npairs * 36; idx += 256) {
-      const int pidx = idx / 36, e = idx % 36, r = e / 6, cc = e % 6;
-      int ii = 0;
-      while ((ii + 1) * (ii + 2) / 2 <= pidx) ++ii;
-      const int jj = pidx - ii * (ii + 1) / 2;
-      const int i = k + 1 + ii, j = k + 1 + jj;
-      const double* Li_ = win + (i % W) * ROWG + (k - i + B) * 36;
-      const double* Lj_ = win + (j % W) * ROWG + (k - j + B) * 36;
-      double sacc = 0.0;
-#pragma unroll
-      for (int m = 0; m < 6; ++m) sacc += Li_[r * 6 + m] * Lj_[cc * 6 + m];
-      win[(i % W) * ROWG + (j - i + B) * 36 + e] -= sacc;
-    }
-    for (int idx = tid; idx < B * 36; idx += 256) {
-      const int q = 1 + idx / 36, e = idx % 36;
-      rec[idx] = (q <= nk) ? win[((k + q) % W) * ROWG + (B - q) * 36 + e] : 0.0;
-    }
-    // row k+B+1 from the staged chunk into row k's slot (first read by the next step's panel)
-    {
-      const double* src = stage + (c & 1) * STG + o * ROWG;
-      for (int idx = tid; idx < ROWG; idx += 256) rk[idx] = src[idx];
-    }
-    if (o == CH - 1) put_stage((c + 1) & 1, pf, CH * ROWG);
-    __syncthreads();
-  }
-  __threadfence();
-  __syncthreads();
-
-  // ---- backward: x_k = L_kk⁻ᵀ (y_k − Σ_q L_(k+q),kᵀ x_(k+q)), column records streamed in reverse ---------
-  auto load_cols = [&](int s0, double* regs) {  // records for steps s0..s0+CH−1, k = N−1−s
-#pragma unroll
-    for (int q = 0; q < PCH; ++q) {
-      const int idx = tid + q * 256;
-      const int sidx = s0 + idx / COLF;
-      regs[q] = (idx < STG && sidx < N) ? a.Lcol[(long long)(N - 1 - sidx) * COLF + idx % COLF] : 0.0;
-    }
-  };
-  if (tid < W * 6) ring[tid] = 0.0;
-  load_cols(0, pf);
-  put_stage(0, pf, STG);
-  __syncthreads();
-  for (int sstep = 0; sstep < N; ++sstep) {
-    const int k = N - 1 - sstep, c = sstep / CH, o = sstep % CH;
-    if (o == 0) load_cols((c + 1) * CH, pf);
-    const double* rec = stage + (c & 1) * STG + o * COLF;
-    if (tid < 6) {
-      const int r = tid;
-      double v = rec[B * 36 + 42 + r];
-#pragma unroll
-      for (int q = 1; q <= B; ++q) {
-        if (k + q >= N) break;
-        const double* Lq = rec + (q - 1) * 36;
-        const double* xq = ring + ((k + q) % W) * 6;
-#pragma unroll
-        for (int m = 0; m < 6; ++m) v -= Lq[m * 6 + r] * xq[m];
-      }
-      sv[r] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double L[36], t[6], id[6];
-#pragma unroll
-      for (int e = 0; e < 36; ++e) L[e] = rec[B * 36 + e];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) { t[r] = sv[r]; id[r] = rec[B * 36 + 36 + r]; }
-#pragma unroll
-      for (int r = 5; r >= 0; --r) {  // L_kkᵀ x = t
-        double v = t[r];
-#pragma unroll
-        for (int m = r + 1; m < 6; ++m) v -= L[m * 6 + r] * t[m];
-        t[r] = v * id[r];
-      }
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        ring[(k % W) * 6 + r] = t[r];
-        a.x[6 * k + r] = t[r];
-      }
-    }
-    if (o == CH - 1) put_stage((c + 1) & 1, pf, STG);
-    __syncthreads();
-  }
-  if (tid == 0) *a.status = 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Block cyclic reduction (bandwidth B ≤ 8 block rows).  Super-row I = block rows [I·B, (I+1)·B) turns the
-// banded reduced camera system into a block-tridiagonal SPD system with m×m blocks (m = 6B): diagonal D_I,
-// coupling U_I = S(I, I+1).  Each level eliminates the odd super-rows j in parallel (one workgroup each:
-// dense Cholesky of D_j in LDS, X_j = D_j⁻¹ [U_{j−1}ᵀ | U_j | b_j]) and rebuilds the even ones
-// (D'_i = D_i − U_{i−1}ᵀ X_{i−1}^U − U_i X_{i+1}^L, U'_i = −U_i X_{i+1}^U, b'_i likewise).  log2(N/B) levels
-// replace the N-step sequential factorisation; back-substitution runs the levels in reverse
-// (x_j = X_j^b − X_j^L x_{j−1} − X_j^U x_{j+1}).
-// ------------------------------------------------------------------------------------------------
-struct CrLevel {
-  double* D;   // n × m²
-  double* U;   // n × m²   (U of the last row = 0)
-  double* b;   // n × m
-  double* X;   // ⌊n/2⌋ × m × (2m+1)
-  double* x;   // n × m
-  int n;
-};
-
-template <int M>
-__global__ __launch_bounds__(256) void cr_build_kernel(const double* __restrict__ Sband, CrLevel L0, int N, int B,
-                                                       int* __restrict__ status) {
-  // one thread per element of D_I, U_I and b_I of level 0 (rows ≥ N are identity padding); the solve's failure flag
-  // is cleared here (the levels only ever set it), which saves a memset launch per solve
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid == 0) *status = 0;
-  const long long nD = (long long)L0.n * M * M;
-  const int ROWG = (B + 1) * 36 + 6;
-  auto lower = [&](int i, int j, int r, int c) -> double {  // S[6i+r][6j+c] for i ≥ j within the band
-    if (i >= N || j >= N) return (i == j && r == c) ? 1.0 : 0.0;
-    if (i - j > B) return 0.0;
-    return Sband[(long long)i * ROWG + (j - i + B) * 36 + r * 6 + c];
-  };
-  if (tid < nD) {
-    const int I = (int)(tid / (M * M)), e = (int)(tid % (M * M)), R = e / M, C = e % M;
-    const int i = I * B + R / 6, j = I * B + C / 6, r = R % 6, c = C % 6;
-    L0.D[tid] = i >= j ? lower(i, j, r, c) : lower(j, i, c, r);
-    // U_I: rows of super-row I, columns of super-row I+1 → S[6i+r][6j'+c] with j' > i
-    const int jn = (I + 1) * B + C / 6;
-    L0.U[tid] = (I + 1 < L0.n) ? lower(jn, i, c, r) : 0.0;
-    return;
-  }
-  const long long t = tid - nD;
-  if (t < (long long)L0.n * M) {
-    const int I = (int)(t / M), R = (int)(t % M), i = I * B + R / 6;
-    L0.b[t] = i < N ? -Sband[(long long)i * ROWG + (B + 1) * 36 + R % 6] : 0.0;
-  }
-}
-
-// Eliminate super-row j (odd rows of the level, or the single root row when `root`): X = D⁻¹ [U_{j−1}ᵀ | U_j | b]
-// by 2×2-block Gauss-Jordan on the augmented M × (3M+1) matrix [D | RHS] (no pivoting: D is SPD, so are its
-// 2×2 pivot blocks).  Lane c owns column c in registers (steps fully unrolled, so every register index is
-// static).  Step k: the pivot columns' owners publish their 2M values to LDS (double-buffered: one barrier per
-// step), every lane reads them as broadcasts and updates its own column.  Measured on MI355X
-// (tools/micro/cr_odd_timing.hip, M = 24): 12 µs per launch for 1×1 pivots against 29 µs for an element-owner
-// formulation whose per-step publish/read traffic was LDS-bound.  A non-positive pivot flags the status.
-template <int M>
-constexpr int kCrOddThreads = ((3 * M + 1) + 63) / 64 * 64;  // one lane per column of [D | RHS], whole waves
-
-// The elimination of one super-row by kCrOddThreads<M> lanes (tid = lane index within that group, c = its
-// column); colk = the group's own publish buffers.  Every lane of the workgroup must call it (barriers).
-// Returns false when a pivot block was not positive definite; a[] = column c of [D⁻¹ | D⁻¹RHS].
-template <int M>
-__device__ __forceinline__ bool gj_row(const CrLevel& L, int j, bool root, int tid, double (*colk)[2][M], double* a) {
-  constexpr int NC = 2 * M + 1, W = M + NC;
-  const int c = min(tid, W - 1);
-  const double* D = L.D + (long long)j * M * M;
-#pragma unroll
-  for (int r = 0; r < M; ++r) {  // all of a lane's loads in flight at once
-    const double* src;
-    if (c < M) src = D + r * M + c;
-    else if (c < 2 * M) src = root ? nullptr : L.U + (long long)(j - 1) * M * M + (c - M) * M + r;  // U_{j−1}ᵀ
-    else if (c < 3 * M) src = (!root && j + 1 < L.n) ? L.U + (long long)j * M * M + r * M + (c - 2 * M) : nullptr;  // U_j
-    else src = L.b + (long long)j * M + r;
-    a[r] = src ? *src : 0.0;
-  }
-  bool bad = false;
-  auto step = [&](int k) {
-    const int buf = (k >> 1) & 1;
-    if (tid == k || tid == k + 1) {
-      double* dst = colk[buf][tid - k];
-#pragma unroll
-      for (int r = 0; r < M; ++r) dst[r] = a[r];
-    }
-    __syncthreads();
-    const double* c0 = colk[buf][0];
-    const double* c1 = colk[buf][1];
-    const double p00 = c0[k], p10 = c0[k + 1], p01 = c1[k], p11 = c1[k + 1];
-    const double det = p00 * p11 - p01 * p10;
-    bad |= !(p00 > 0.0 && det > 0.0);
-    const double rd = rcp_nr(det);
-    double ak = a[0], ak1 = a[1];
-#pragma unroll
-    for (int r = 1; r < M; ++r) ak = r == k ? a[r] : ak;
-#pragma unroll
-    for (int r = 2; r < M; ++r) ak1 = r == k + 1 ? a[r] : ak1;
-    const double t0 = (p11 * ak - p01 * ak1) * rd;
-    const double t1 = (p00 * ak1 - p10 * ak) * rd;
-#pragma unroll
-    for (int r = 0; r < M; ++r) a[r] = r == k ? t0 : (r == k + 1 ? t1 : a[r] - c0[r] * t0 - c1[r] * t1);
-  };
-  if constexpr (M <= 24) {
-#pragma unroll
-    for (int k = 0; k < M; k += 2) step(k);
-  } else {
-#pragma unroll 1
-    for (int k = 0; k < M; k += 2) step(k);
-  }
-  return !bad;
-}
-
-// One level of cyclic reduction in ONE launch: workgroup i/2 rebuilds even super-row i.  Its two halves
-// eliminate the neighbouring odd rows i−1 and i+1 side by side (gj_row, redundantly with the neighbouring
-// workgroups — each odd row is done twice, saving a launch and an HBM round trip of X per level), keep both X in
-// LDS, store X_{i+1} for the back-substitution (every odd row is the right neighbour of exactly one even row),
-// then form D'_i = D_i − U_{i−1}ᵀX^U_{i−1} − U_i X^L_{i+1}, U'_i = −U_i X^U_{i+1} and b'_i likewise.
-template <int M>
-constexpr size_t cr_level_lds() { return sizeof(double) * (2 * M * M + 2 * M * (2 * M + 1)); }
-
-template <int M>
-__global__ __launch_bounds__(2 * kCrOddThreads<M>) void cr_level_kernel(CrLevel L, CrLevel Ln, int* status) {
-  constexpr int NC = 2 * M + 1, W = M + NC, T = kCrOddThreads<M>;
-  __shared__ __attribute__((aligned(16))) double colk[2][2][2][M];
-  extern __shared__ double smem[];
-  double* sUl = smem;               // U_{i−1}   M×M
-  double* sUi = sUl + M * M;        // U_i       M×M
-  double* sX[2] = {sUi + M * M, sUi + M * M + M * NC};  // X_{i−1}, X_{i+1}   M×NC each
-  const int i = 2 * blockIdx.x, in = blockIdx.x;
-  const int half = threadIdx.x >= T ? 1 : 0, tl = threadIdx.x - half * T;
-  const int j = half ? i + 1 : i - 1;
-  const bool has = j >= 0 && j < L.n;
-  double a[M];
-  const bool ok = gj_row<M>(L, has ? j : 1, false, tl, colk[half], a);
-  if (!ok && has && tl == 0) atomicOr(status, 1);
-  if (tl >= M && tl < W) {
-    double* x = sX[half] + (tl - M);
-#pragma unroll
-    for (int r = 0; r < M; ++r) x[r * NC] = has ? a[r] : 0.0;
-    if (half && has) {
-      double* X = L.X + (long long)(j / 2) * M * NC + (tl - M);
-#pragma unroll
-      for (int r = 0; r < M; ++r) X[r * NC] = a[r];
-    }
-  }
-  const bool left = i - 1 >= 0, right = i + 1 < L.n;
-  for (int e = threadIdx.x; e < M * M; e += 2 * T) {
-    sUl[e] = left ? L.U[(long long)(i - 1) * M * M + e] : 0.0;
-    sUi[e] = L.U[(long long)i * M * M + e];
-  }
-  __syncthreads();
-  const double* sXl = sX[0];
-  const double* sXr = sX[1];
-  for (int e = threadIdx.x; e < 2 * M * M + M; e += 2 * T) {
-    if (e < M * M) {  // D' = D − U_{i−1}ᵀ X^U_{i−1} − U_i X^L_{i+1}
-      const int r = e / M, c = e % M;
-      double v = L.D[(long long)i * M * M + e];
-#pragma unroll 8
-      for (int q = 0; q < M; ++q) v -= sUl[q * M + r] * sXl[q * NC + M + c] + sUi[r * M + q] * sXr[q * NC + c];
-      Ln.D[(long long)in * M * M + e] = v;
-    } else if (e < 2 * M * M) {  // U' = −U_i X^U_{i+1}
-      const int f = e - M * M, r = f / M, c = f % M;
-      double v = 0.0;
-#pragma unroll 8
-      for (int q = 0; q < M; ++q) v -= sUi[r * M + q] * sXr[q * NC + M + c];
-      Ln.U[(long long)in * M * M + f] = right ? v : 0.0;
-    } else {  // b'
-      const int r = e - 2 * M * M;
-      double v = L.b[(long long)i * M + r];
-#pragma unroll 8
-      for (int q = 0; q < M; ++q) v -= sUl[q * M + r] * sXl[q * NC + 2 * M] + sUi[r * M + q] * sXr[q * NC + 2 * M];
-      Ln.b[(long long)in * M + r] = v;
-    }
-  }
-}
-
-// Wave-level variant for super-rows of ≤ 31 unknowns (B ≤ 5 keyframes), where [D | one coupling block | b] fits one
-// wave: lane c < M holds column c of D, lanes M…2M−1 the coupling block's columns, lane 2M b.  The pivot columns are
-// then always in the elimination's own wave: the pivot lanes publish them to a per-wave LDS buffer and every lane
-// reads them back with no s_barrier (LDS operations of one wave are processed in order).  Measured
-// (tools/micro/cr_level_timing.hip, M = 24): 17.0 → 14.5 µs per level launch with 2-column pivots (13.0 with the
-// rebuild on the matrix cores, below); 4-column pivot blocks (6 publish/read round trips instead of 12): C4 step
-// 0.228 → 0.216 ms per LM iteration (8-column blocks: 0.216-0.220, their per-lane 8×8 solve costs what the saved
-// round trips gain).
-#ifndef PBA_CR_PIVOT
-#define PBA_CR_PIVOT 4
-#endif
-constexpr int kCrPivot = PBA_CR_PIVOT;  // columns per Gauss-Jordan step of gj_wave (1, 2, 4 or 8; divides M)
-
-// Loads of the rows a launch wrote itself (COH: the last PCR level's solve reads the rows its own workgroup has just
-// stored, cr_level_wave_kernel): `sc1` (L1-bypassing) agent-scope loads; plain otherwise.
-template <bool COH>
-__device__ __forceinline__ double ld_row(const double* p) {
-  if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else return *p;
-}
-
-// Pivot blocks of PB columns: lanes k … k+PB−1 publish their columns to the wave's LDS buffer (row r: PB doubles),
-// every lane reads the PB×PB pivot block P and solves P t = a[k … k+PB−1] in registers (unpivoted Gauss-Jordan:
-// D is SPD, so is every pivot block; all of P's pivots must be positive), then updates its other rows
-// a[r] −= Σ_j piv[r][j] t_j.  The publish / read round trip is paid M/PB times instead of M/2 times; the updates are
-// the same FMAs.
-// b: NB right-hand-side columns, row-major (row r of column q at b[r·NB + q]); lanes 2M … M + ncol − 1 take them.
-template <int M, bool COH = false, int PB = kCrPivot, int NB = 1>
-__device__ __forceinline__ bool gj_wave(const double* __restrict__ D, const double* __restrict__ R1, bool r1_trans,
-                                        const double* __restrict__ b, int ncol, int c, double* piv, double* a) {
-  static_assert(M % PB == 0, "pivot blocks tile the system");
-  // column c of [D | R1 | b] as base + r·stride: one address choice per lane, then M unconditional loads in flight
-  // together (a lane without a column reads D's and keeps zeros)
-  const double* base = D + min(c, M - 1);
-  int stride = M;
-  bool zero = c >= M + ncol;
-  if (c >= M && c < 2 * M) {
-    if (R1) {
-      base = r1_trans ? R1 + (c - M) * M : R1 + (c - M);
-      stride = r1_trans ? 1 : M;
-    } else {
-      zero = true;
-    }
-  } else if (c >= 2 * M && c < M + ncol) {
-    if (b) {
-      base = b + (c - 2 * M);
-      stride = NB;
-    } else {
-      zero = true;
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < M; ++r) a[r] = ld_row<COH>(base + r * stride);
-#pragma unroll
-  for (int r = 0; r < M; ++r) a[r] = zero ? 0.0 : a[r];
-  bool bad = false;
-#pragma unroll
-  for (int k = 0; k < M; k += PB) {
-    if (c >= k && c < k + PB) {
-      double* dst = piv + (c - k);
-#pragma unroll
-      for (int r = 0; r < M; ++r) dst[PB * r] = a[r];
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-    // every pivot row of the step read at once (the pivot block's rows first): the 24·PB broadcast reads are in flight
-    // during the PB×PB solve instead of one or two at a time between the update FMAs (the update was LDS-latency
-    // bound: ~2200 cycles per step)
-    double pr[M][PB];
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      const int r = (i + k) % M;
-#pragma unroll
-      for (int j = 0; j < PB; ++j) pr[r][j] = piv[PB * r + j];
-    }
-    double P[PB][PB], t[PB];
-#pragma unroll
-    for (int i = 0; i < PB; ++i) {
-#pragma unroll
-      for (int j = 0; j < PB; ++j) P[i][j] = pr[k + i][j];
-      t[i] = a[k + i];
-    }
-#pragma unroll
-    for (int i = 0; i < PB; ++i) {  // t ← P⁻¹ t
-      bad |= !(P[i][i] > 0.0);
-      const double inv = rcp_nr(P[i][i]);
-#pragma unroll
-      for (int j = i + 1; j < PB; ++j) P[i][j] *= inv;
-      t[i] *= inv;
-#pragma unroll
-      for (int q = 0; q < PB; ++q) {
-        if (q == i) continue;
-        const double f = P[q][i];
-#pragma unroll
-        for (int j = i + 1; j < PB; ++j) P[q][j] -= f * P[i][j];
-        t[q] -= f * t[i];
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < M; ++r) {
-      if (r >= k && r < k + PB) {
-        a[r] = t[r - k];
-      } else {
-        double v = a[r];
-#pragma unroll
-        for (int j = 0; j < PB; ++j) v -= pr[r][j] * t[j];
-        a[r] = v;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-  }
-  return !bad;
-}
-
-
-// Rebuild of super-row i (next-level index in) from the two eliminations in LDS (sXl = X_{i−1}, sXr = X_{i+1}) and
-// U_{i−1}, U_i, D_i, b_i, on RB waves: 4 waves take two column tiles each, 8 waves one.  keep_u: the rebuilt row
-// still has a right coupling.  Waves w ≥ RB return at once.
-template <int M, int RB, int NB = 1>
-__device__ __forceinline__ void cr_rebuild(int w, int lane, const double* sUl, const double* sUi, const double* sD,
-                                           const double* sb, const double* sXl, const double* sXr, const CrLevel& Ln,
-                                           int in, bool keep_u) {
-  constexpr int NC = 2 * M + NB;  // [D | U | b] columns: b's NB columns at 2M …
-  static_assert(NC <= 64, "four column tiles");
-  // Rebuild of row i on the matrix cores: [D' | U' | b'] = [D | 0 | b] − U_{i−1}ᵀ·[X^U_{i−1} | 0 | X^b_{i−1}]
-  // − U_i·X_{i+1}, as 2 × 4 output tiles of v_mfma_f64_16x16x4f64 (rows padded to 32, columns to 64).  Wave w takes
-  // row tile w & 1 and column tiles TPW·(w >> 1) + {0 … TPW−1}: a wave's tiles share the A operands and run as
-  // independent accumulator chains.  Layouts (tools/micro/mfma_f64_layout.hip): A lane l = (row l%16, k l/16),
-  // B lane l = (k l/16, column l%16), accumulator entry v of lane l = (row l/16 + 4v, column l%16).
-  // 3.9 → 2.7 µs per level against the scalar LDS products (tools/micro/cr_level_timing.hip, V5).
-  static_assert(M % 4 == 0 && M <= 32, "K steps of 4, two row tiles");
-  static_assert(RB == 4 || RB == 8, "2 × 4 tiles over the rebuild waves");
-  constexpr int TPW = 8 / RB;  // column tiles per wave
-  if (w >= RB) return;
-  const int rt = w & 1;
-  const int arow = 16 * rt + (lane & 15), kq = lane >> 4;
-  // every operand of the six K steps read from LDS first, at clamped (in-range) indices and with unconditional reads,
-  // then the padding zeroed by selects: conditional reads were issued and waited one at a time (~2.9 µs per level)
-  constexpr int KS = M / 4;
-  const bool aok = arow < M;
-  const int ar = aok ? arow : 0;
-  int bcol[TPW];
-  double av2[KS], av1[KS], bv2[TPW][KS], bv1[TPW][KS], cv[TPW][4];
-#pragma unroll
-  for (int h = 0; h < TPW; ++h) {
-    bcol[h] = 16 * ((w >> 1) * TPW + h) + (lane & 15);
-    const int c = bcol[h];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int r = 16 * rt + (lane >> 4) + 4 * v;
-      cv[h][v] = c < M ? sD[min(r, M - 1) * M + c] : sb[min(r, M - 1) * NB + min(max(c - 2 * M, 0), NB - 1)];
-    }
-  }
-#pragma unroll
-  for (int s4 = 0; s4 < KS; ++s4) {
-    const int q = 4 * s4 + kq;
-    av2[s4] = sUi[ar * M + q];
-    av1[s4] = sUl[q * M + ar];
-#pragma unroll
-    for (int h = 0; h < TPW; ++h) {
-      const int c = bcol[h];
-      bv2[h][s4] = sXr[q * NC + min(c, NC - 1)];
-      bv1[h][s4] = sXl[q * NC + (c < M ? M + c : min(max(c, 2 * M), NC - 1))];
-    }
-  }
-  v4f64 acc[TPW];
-#pragma unroll
-  for (int h = 0; h < TPW; ++h) {
-    const int c = bcol[h];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int r = 16 * rt + (lane >> 4) + 4 * v;
-      acc[h][v] = (r < M && (c < M || (c >= 2 * M && c < NC))) ? cv[h][v] : 0.0;
-    }
-  }
-#pragma unroll
-  for (int s4 = 0; s4 < KS; ++s4) {
-    const double a2 = aok ? -av2[s4] : 0.0;
-    const double a1 = aok ? -av1[s4] : 0.0;
-#pragma unroll
-    for (int h = 0; h < TPW; ++h) {
-      const int c = bcol[h];
-      const double b2 = c < NC ? bv2[h][s4] : 0.0;
-      const double b1 = (c < M || (c >= 2 * M && c < NC)) ? bv1[h][s4] : 0.0;
-      acc[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, acc[h], 0, 0, 0);
-      acc[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[h], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int h = 0; h < TPW; ++h)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int r = 16 * rt + (lane >> 4) + 4 * v, c = bcol[h];
-      if (r < M) {
-        if (c < M) Ln.D[(long long)in * M * M + r * M + c] = acc[h][v];
-        else if (c < 2 * M) Ln.U[(long long)in * M * M + r * M + (c - M)] = keep_u ? acc[h][v] : 0.0;
-        else if (c < NC) Ln.b[((long long)in * M + r) * NB + (c - 2 * M)] = acc[h][v];
-      }
-    }
-}
-
-// per-wave LDS of an elimination: gj_wave's pivot columns
-template <int M>
-constexpr int kPivBuf = M * kCrPivot;
-
-template <int M, int NB = 1>
-constexpr size_t cr_level_wave_lds() { return sizeof(double) * (3 * M * M + M * NB + 2 * M * (2 * M + NB)); }
-
-// One level, 4 waves per rebuilt super-row i: wave 0 eliminates its left neighbour l on [D | U_l | b] (X^U, X^b),
-// waves 1 and 2 its right neighbour r on [D | U_iᵀ | b] (X^L, X^b) and [D | U_r] (X^U) — D's columns replicated per
-// wave — while wave 3 parks U_l, U_i, D_i and b_i in LDS for the rebuild of row i.
-//   CR  (PCR = false): i = 2·blockIdx (the even rows), l = i − 1, r = i + 1, rebuilt row i/2 of the next level; X_r
-//       is stored for the back-substitution.
-//   PCR (PCR = true, stride s): i = blockIdx (EVERY row), l = i − s, r = i + s, rebuilt row i of the next level
-//       (couplings now at stride 2s).  Every row stays in the system, so after ⌈log2 n⌉ levels all couplings are
-//       gone and x_i = D_i⁻¹ b_i (pcr_solve_kernel): no back-substitution.  A PCR level runs twice the workgroups of a
-//       CR level at the same per-workgroup latency, so it is used while the rows fit one workgroup per CU.
-// The D_i' are Schur complements of SPD principal submatrices ({l, i, r}), so every pivot block stays SPD.
-// The level's work for row i (rebuilt as row `in` of Ln) by a 4-wave workgroup: piv = 3 × M·kCrPivot doubles, smem =
-// cr_level_wave_lds<M>() bytes.
-// NB > 1 (PCR only): b holds NB right-hand-side columns (row-major, b[(i·M + r)·NB + q]) — the free-intrinsics
-// arrow solve's [−g | border columns] (arrow_solve).
-template <int M, bool PCR, int NB = 1>
-__device__ __forceinline__ void cr_wave_level(const CrLevel& L, const CrLevel& Ln, int i, int in, int s, int* status,
-                                              double (*piv)[kPivBuf<M>], double* smem) {
-  static_assert(2 * M + NB <= 64, "one wave per elimination");
-  static_assert(PCR || NB == 1, "the back-substitution's X has one right-hand side");
-  constexpr int NC = 2 * M + NB;
-  double* sUl = smem;
-  double* sUi = sUl + M * M;
-  double* sD = sUi + M * M;
-  double* sb = sD + M * M;
-  double* sX[2] = {sb + M * NB, sb + M * NB + M * NC};
-  const int il = i - s, ir = i + s;
-  const bool left = il >= 0, right = ir < L.n;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#ifdef PBA_CR_STAMPS
-  long long t0 = wall_clock64(), t1 = 0, t2 = 0;
-#endif
-  if (w == 3) {
-    // U_l, U_i, D_i, b_i → LDS: every load in flight at once (a loop of load → LDS store pays one memory round trip
-    // per element, serially: measured ~10 µs of a 12.4-µs level); missing neighbours read U_i and store zeros
-    constexpr int NE = 3 * M * M + M * NB, NQ = (NE + 63) / 64;
-    double v[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int e = lane + 64 * q;
-      const double* src = L.b + (long long)i * M * NB;
-      if (e < M * M) src = L.U + (long long)(left ? il : i) * M * M + e;
-      else if (e < 2 * M * M) src = L.U + (long long)i * M * M + (e - M * M);
-      else if (e < 3 * M * M) src = L.D + (long long)i * M * M + (e - 2 * M * M);
-      else if (e < NE) src = L.b + (long long)i * M * NB + (e - 3 * M * M);
-      v[q] = *src;
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int e = lane + 64 * q;
-      const bool zero = (e < M * M && !left) || (e >= M * M && e < 2 * M * M && !right);
-      if (e < NE) smem[e] = zero ? 0.0 : v[q];
-    }
-  } else {
-    const int j = w == 0 ? il : ir;
-    const bool has = w == 0 ? left : right;
-    const int jj = has ? j : i;  // a missing neighbour eliminates a real row and contributes zeros
-    const double* D = L.D + (long long)jj * M * M;
-    const double* bj = L.b + (long long)jj * M * NB;
-    double a[M];
-    bool ok;
-    if (w == 0) ok = gj_wave<M, false, kCrPivot, NB>(D, L.U + (long long)jj * M * M, false, bj, M + NB, lane, piv[0], a);
-    else if (w == 1) ok = gj_wave<M, false, kCrPivot, NB>(D, L.U + (long long)i * M * M, true, bj, M + NB, lane, piv[1], a);
-    else ok = gj_wave<M>(D, jj + s < L.n ? L.U + (long long)jj * M * M : nullptr, false, nullptr, M, lane, piv[2], a);
-    if (!ok && has && lane == 0) atomicOr(status, 1);
-    if (lane >= M && lane < 2 * M + (w == 2 ? 0 : NB)) {
-      const int col = lane < 2 * M ? (w == 1 ? lane - M : lane) : lane;  // (b's columns keep their lane index)
-      double* x = sX[w == 0 ? 0 : 1] + col;
-#pragma unroll
-      for (int r = 0; r < M; ++r) x[r * NC] = has ? a[r] : 0.0;
-      if (!PCR && w != 0 && has) {  // X_{i+1} for the back-substitution
-        double* X = L.X + (long long)(j / 2) * M * NC + col;
-#pragma unroll
-        for (int r = 0; r < M; ++r) X[r * NC] = a[r];
-      }
-    }
-  }
-#ifdef PBA_CR_STAMPS
-  t1 = wall_clock64();
-#endif
-  __syncthreads();
-#ifdef PBA_CR_STAMPS
-  t2 = wall_clock64();
-#endif
-  cr_rebuild<M, 4, NB>(w, lane, sUl, sUi, sD, sb, sX[0], sX[1], Ln, in, PCR ? i + 2 * s < L.n : right);
-#ifdef PBA_CR_STAMPS
-  __syncthreads();
-  const long long t3 = wall_clock64();
-  if (blockIdx.x == 5 && lane == 0)
-    printf("crstamp s=%d w=%d phase_end_us %.2f barrier_us %.2f rebuild_us %.2f\n", s, w, (t1 - t0) * 0.01,
-           (t2 - t0) * 0.01, (t3 - t0) * 0.01);
-#endif
-}
-
-// out != nullptr (the last PCR level): the workgroup then also solves its decoupled row, x_i = D'_i⁻¹ b'_i, from the
-// rows it has just written (read back with L1-bypassing loads after every wave's stores completed) — pcr_solve_kernel's
-// work without its launch boundary and its reload of the level (out / lim as pcr_solve_kernel).
-// NB > 1: out row t = i·M + r holds the NB solution columns at out[t·ld + q].
-// Several independent right-hand-side batches in one launch (the arrow solve, gridDim.y = batches): batch y reads L's
-// D, U at + y·bs_du and b at + y·bs_b, writes Ln at + y·bs_n and its solution columns at out + y·NB (its own CR run
-// over its own copies of the rows: the batches share only L when that is level 0).
-template <int M, bool PCR, int NB = 1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void cr_level_wave_kernel(
-    CrLevel L, CrLevel Ln, int s, int* status, double* __restrict__ out, int lim, int ld = 1, long long bs_du = 0,
-    long long bs_b = 0, long long bs_n = 0) {
-  __shared__ __attribute__((aligned(16))) double piv[3][kPivBuf<M>];
-  extern __shared__ double smem[];
-  if (blockIdx.y) {
-    const long long y = blockIdx.y;
-    L.D += y * bs_du;
-    L.U += y * bs_du;
-    L.b += y * bs_b;
-    Ln.D += y * bs_n;
-    Ln.U += y * bs_n;
-    Ln.b += y * bs_n;
-    if (out) out += y * NB;
-  }
-  const int i = PCR ? (int)blockIdx.x : 2 * (int)blockIdx.x;
-  cr_wave_level<M, PCR, NB>(L, Ln, i, blockIdx.x, PCR ? s : 1, status, piv, smem);
-  if (!PCR || !out) return;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's row stores have completed
-  __syncthreads();
-  if (threadIdx.x >= 64) return;
-  const int lane = threadIdx.x;
-  double a[M];
-  const bool ok = gj_wave<M, true, kCrPivot, NB>(Ln.D + (long long)i * M * M, nullptr, false, Ln.b + (long long)i * M * NB,
-                                                 M + NB, lane, piv[0], a);
-  if (!ok) {
-    if (lane == 0) atomicOr(status, 1);
-    return;
-  }
-  if (lane >= 2 * M && lane < 2 * M + NB)
-#pragma unroll
-    for (int r = 0; r < M; ++r)
-      if (i * M + r < lim) out[((long long)i * M + r) * ld + (lane - 2 * M)] = a[r];
-}
-
-// The root super-row on one wave (lane 2M carries b; the coupling lanes are empty).
-template <int M>
-__global__ __launch_bounds__(64) void cr_root_wave_kernel(CrLevel L, int* status) {
-  __shared__ __attribute__((aligned(16))) double piv[kPivBuf<M>];
-  double a[M];
-  const int lane = threadIdx.x;
-  const bool ok = gj_wave<M>(L.D, nullptr, false, L.b, M + 1, lane, piv, a);
-  if (!ok) {
-    if (lane == 0) atomicOr(status, 1);
-    return;
-  }
-  if (lane == 2 * M)
-#pragma unroll
-    for (int r = 0; r < M; ++r) L.x[r] = a[r];
-}
-
-// The last PCR level's decoupled rows: x_i = D_i⁻¹ b_i, one wave per row; x in the level-0 layout is the step itself
-// (out = the step vector, lim = 6N), else the x of the CR level the PCR levels took over from.
-template <int M, int NB = 1>
-__global__ __launch_bounds__(64) void pcr_solve_kernel(CrLevel L, double* __restrict__ out, int lim, int* status,
-                                                       int ld = 1) {
-  __shared__ __attribute__((aligned(16))) double piv[kPivBuf<M>];
-  const int lane = threadIdx.x, i = blockIdx.x;
-  double a[M];
-  const bool ok = gj_wave<M, false, kCrPivot, NB>(L.D + (long long)i * M * M, nullptr, false, L.b + (long long)i * M * NB,
-                                                  M + NB, lane, piv, a);
-  if (!ok) {
-    if (lane == 0) atomicOr(status, 1);
-    return;
-  }
-  if (lane >= 2 * M && lane < 2 * M + NB)
-#pragma unroll
-    for (int r = 0; r < M; ++r)
-      if (i * M + r < lim) out[((long long)i * M + r) * ld + (lane - 2 * M)] = a[r];
-}
-
-// The root super-row (the last level): x = D⁻¹ b.
-template <int M>
-__global__ __launch_bounds__(kCrOddThreads<M>) void cr_root_kernel(CrLevel L, int* status) {
-  constexpr int W = 3 * M + 1;
-  __shared__ __attribute__((aligned(16))) double colk[2][2][M];
-  double a[M];
-  const bool ok = gj_row<M>(L, 0, true, threadIdx.x, colk, a);
-  if (!ok) {  // uniform: every lane saw the same pivots
-    if (threadIdx.x == 0) atomicOr(status, 1);
-    return;
-  }
-  if ((int)threadIdx.x == W - 1)
-#pragma unroll
-    for (int r = 0; r < M; ++r) L.x[r] = a[r];
-}
-
-// Back-substitution, level L from level L+1: x_j = X_j^b − X_j^L x_{j−1} − X_j^U x_{j+1} for the odd rows, x of the
-// even rows from the next level.  Level 0's x is the step δ itself (super-row I, element R ↔ block row
-// I·B + R/6, component R%6), so it is written straight into the step vector.  The small levels at the bottom
-// (n ≤ kCrTailRows) run in ONE workgroup with barriers between levels — one launch instead of one per level.
-constexpr int kMaxCrLevels = 26;
-constexpr int kCrTailRows = 32;
-struct CrLevels {
-  CrLevel lv[kMaxCrLevels];
-  int nl;
-};
-
-template <int M>
-__device__ __forceinline__ void cr_back_row(const CrLevel& L, const double* __restrict__ xn, double* out, int t) {
-  constexpr int NC = 2 * M + 1;
-  const int row = t / M, r = t % M;
-  double v;
-  if ((row & 1) == 0) {
-    v = xn[(row / 2) * M + r];
-  } else {
-    const double* X = L.X + (long long)(row / 2) * M * NC + r * NC;
-    v = X[2 * M];
-    const double* xl = xn + ((row - 1) / 2) * M;
-#pragma unroll 8
-    for (int c = 0; c < M; ++c) v -= X[c] * xl[c];
-    if (row + 1 < L.n) {
-      const double* xr = xn + ((row + 1) / 2) * M;
-#pragma unroll 8
-      for (int c = 0; c < M; ++c) v -= X[M + c] * xr[c];
-    }
-  }
-  out[t] = v;
-}
-
-// one (large) level, one lane per output
-template <int M>
-__global__ void cr_back_kernel(CrLevel L, const double* __restrict__ xn, double* __restrict__ out, int lim) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < lim) cr_back_row<M>(L, xn, out, t);
-}
-
-// levels hi … lo (all small) in one workgroup
-template <int M>
-__global__ __launch_bounds__(1024) void cr_back_tail_kernel(const CrLevels C, int hi, int lo, double* __restrict__ step,
-                                                            int N) {
-  for (int l = hi; l >= lo; --l) {
-    const CrLevel& L = C.lv[l];
-    double* out = l == 0 ? step : L.x;
-    const int lim = l == 0 ? 6 * N : L.n * M;
-    for (int t = threadIdx.x; t < lim; t += blockDim.x) cr_back_row<M>(L, C.lv[l + 1].x, out, t);
-    __syncthreads();  // this level's x is read by the next (lower) level
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Free intrinsics as an arrow system (map_utils.h:339-345)
-// ------------------------------------------------------------------------------------------------
-// With free intrinsics the reduced camera system is S = [A B; Bᵀ C]: A the keyframes' band (bandwidth ≤ 4 keyframes), B
-// the 2·nc border frames' coupling to every keyframe (dense columns), C the border's own 12nc × 12nc block.  The skyline
-// factorisation (front_solve_kernel) walks the whole system column by column — one workgroup, ~3.5 µs per keyframe,
-// 3.64 ms at C4.  Eliminating the keyframes first is the same factorisation order (border last), so instead:
-//   X = A⁻¹ [−g_a | B]          parallel cyclic reduction over the band, the border's 12nc columns as extra right-hand
-//                               sides (cr_level_wave_kernel<24, true, kArrowNB>: [D | U | b] = 24 + 24 + 16 lanes),
-//                               in batches of kArrowNB columns run side by side (gridDim.y);
-//   Sc = C − BᵀX_B,  rc = −g_c − BᵀX_0,  δc = Sc⁻¹ rc     (arrow_reduce_kernel: a workgroup per product;
-//                               arrow_cap_kernel: one workgroup, dense Cholesky of the ≤ 48 × 48 border system);
-//   δa = X_0 − X_B δc           (arrow_back_kernel).
-// The skyline S stays the assembled system (pba_gn_reduced_system, the multi-GPU export read it), g its gradient.
-constexpr int kArrowNB = 16;   // right-hand-side columns per cyclic-reduction run (2·24 + 16 = 64 lanes)
-constexpr int kArrowMaxNc = 4; // border of ≤ 48 unknowns (arrow_cap_kernel's LDS system)
-
-struct ArrowArgs {
-  const double* S;       // skyline system (lower blocks; block (i, j) at (row[i] + j − first[i])·36, element r·6 + c)
-  const int* first;
-  const int* row;
-  const double* g;       // gradient, 6 per system frame
-  const uint8_t* fixed;  // constant keyframes (their border coupling is dropped: identity rows of S)
-  CrLevel L0;            // level 0 of the band (D, U, b of kArrowNB columns)
-  double* X;             // 6·nf rows × ldx: A⁻¹[−g_a | B]
-  double* part;          // kArrowSeg × n_ent partial products (arrow_reduce_kernel)
-  double* dc;            // the border step (12nc)
-  double* x;             // the step, 6 per system frame
-  int* status;
-  int nf, nc, ldx, n_ent;
-};
-
-// Level 0 of the band (super-rows of 4 keyframes, identity padding past the last keyframe) and the batch's kArrowNB
-// right-hand-side columns: global column 0 = −g_a, 1 + q = column q of B (border frame nf + q/6, component q % 6),
-// B[6f + r][q] = S(border row, keyframe f)[q % 6][r].  Every batch's columns in one launch: batch bt's b at
-// L0.b + bt·n·M·kArrowNB (the batches share level 0's D and U).
-__device__ __forceinline__ void arrow_build(const ArrowArgs& a, int batches, long long tid) {
-  constexpr int M = 24, B = 4, NB = kArrowNB;
-  const int n = a.L0.n;
-  if (tid == 0) *a.status = 0;
-  auto blk = [&](int i, int j, int r, int c) -> double {  // S[6i + r][6j + c], i ≥ j, 0 outside the profile
-    return j >= a.first[i] ? a.S[((long long)a.row[i] + (j - a.first[i])) * 36 + r * 6 + c] : 0.0;
-  };
-  const long long nDU = (long long)n * M * M;
-  if (tid < 2 * nDU) {
-    const bool isU = tid >= nDU;
-    const long long e0 = isU ? tid - nDU : tid;
-    const int I = (int)(e0 / (M * M)), e = (int)(e0 % (M * M)), R = e / M, C = e % M;
-    const int i = I * B + R / 6, r = R % 6, c = C % 6;
-    double v;
-    if (!isU) {
-      const int j = I * B + C / 6;
-      if (i >= a.nf || j >= a.nf) v = (i == j && r == c) ? 1.0 : 0.0;
-      else v = i >= j ? blk(i, j, r, c) : blk(j, i, c, r);
-      a.L0.D[e0] = v;
-    } else {
-      const int j = (I + 1) * B + C / 6;
-      a.L0.U[e0] = (I + 1 < n && i < a.nf && j < a.nf) ? blk(j, i, c, r) : 0.0;
-    }
-    return;
-  }
-  const long long t = tid - 2 * nDU;
-  if (t >= (long long)batches * n * M * NB) return;
-  const int q = (int)(t % NB), R = (int)((t / NB) % M), I = (int)((t / ((long long)NB * M)) % n);
-  const int batch = (int)(t / ((long long)n * M * NB));
-  const int i = I * B + R / 6, r = R % 6, gq = NB * batch + q;
-  double v = 0.0;
-  if (i < a.nf && !a.fixed[i]) {
-    if (gq == 0) v = -a.g[6 * i + r];
-    else if (gq <= 12 * a.nc) v = blk(a.nf + (gq - 1) / 6, i, (gq - 1) % 6, r);
-  }
-  a.L0.b[t] = v;
-}
-__global__ __launch_bounds__(256) void arrow_build_kernel(const ArrowArgs a, int batches) {
-  arrow_build(a, batches, (long long)blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-// kArrowSeg workgroups per product: entry e < nb(nb+1)/2 — (q1 ≥ q2) of BᵀX_B — then e − that: q1 of BᵀX_0 (nb = 12nc), a
-// dot product over the T = 6nf keyframe rows; workgroup (e, g) takes segment g of the rows (thread k: rows k, k + 256, …
-// of it; xor butterflies per wave, the four waves in order) → part[g·n_ent + e]; arrow_cap_kernel adds the kArrowSeg
-// segments in order (a fixed order).
-constexpr int kArrowSeg = 8;
-__global__ __launch_bounds__(256) void arrow_reduce_kernel(const ArrowArgs a) {
-  __shared__ double s_w[4];
-  const int nb = 12 * a.nc, nsym = nb * (nb + 1) / 2, T = 6 * a.nf, e = blockIdx.x, g = blockIdx.y;
-  const int t0 = (int)((long long)g * T / kArrowSeg), t1 = (int)((long long)(g + 1) * T / kArrowSeg);
-  int q1, xc;
-  if (e < nsym) {
-    q1 = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-    while (q1 * (q1 + 1) / 2 > e) --q1;
-    while ((q1 + 1) * (q1 + 2) / 2 <= e) ++q1;
-    xc = 1 + (e - q1 * (q1 + 1) / 2);  // X column of q2
-  } else {
-    q1 = e - nsym;
-    xc = 0;
-  }
-  const int p = a.nf + q1 / 6, c = q1 % 6;
-  const double* Sp = a.S + (long long)a.row[p] * 36 + c * 6;  // border row p starts at frame 0
-  double acc = 0.0;
-  for (int tt = t0 + (int)threadIdx.x; tt < t1; tt += 256)
-    acc += Sp[(long long)(tt / 6) * 36 + tt % 6] * a.X[(long long)tt * a.ldx + xc];
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) a.part[(long long)g * a.n_ent + e] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-
-// The border system Sc = C − BᵀX_B, rc = −g_c − BᵀX_0, its elimination in LDS and δc = Sc⁻¹ rc (the border's part of
-// the step); one workgroup.  (A one-wave form without workgroup barriers measured no faster: 15.4 → 17.0 µs at C4.)
-__global__ __launch_bounds__(256) void arrow_cap_kernel(const ArrowArgs a) {
-  constexpr int NBM = 12 * kArrowMaxNc;
-  __shared__ double sc[NBM][NBM + 1];
-  __shared__ double rc[NBM];
-  __shared__ int bad;
-  const int nb = 12 * a.nc, nsym = nb * (nb + 1) / 2, tid = threadIdx.x;
-  if (tid == 0) bad = 0;
-  for (int e = tid; e < a.n_ent; e += blockDim.x) {
-    double acc = a.part[e];
-    for (int g = 1; g < kArrowSeg; ++g) acc += a.part[(long long)g * a.n_ent + e];
-    if (e < nsym) {
-      int q1 = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-      while (q1 * (q1 + 1) / 2 > e) --q1;
-      while ((q1 + 1) * (q1 + 2) / 2 <= e) ++q1;
-      const int q2 = e - q1 * (q1 + 1) / 2;
-      const int p1 = a.nf + q1 / 6, c1 = q1 % 6, p2 = a.nf + q2 / 6, c2 = q2 % 6;  // p1 ≥ p2
-      const double C = a.S[((long long)a.row[p1] + (p2 - a.first[p1])) * 36 + c1 * 6 + c2];
-      sc[q1][q2] = sc[q2][q1] = C - acc;
-    } else {
-      const int q1 = e - nsym;
-      rc[q1] = -a.g[6 * (a.nf + q1 / 6) + q1 % 6] - acc;
-    }
-  }
-  __syncthreads();
-  // Gauss-Jordan on [Sc | rc] with one barrier per column (no serial triangular solves: a one-lane substitution paid an
-  // LDS round trip per term, ~nb² of them — 30 µs at nb = 24): step k takes every row i ≠ k's columns j > k and rc,
-  // a_ij −= a_ik·a_kj / a_kk; column k and row k are only read in step k, so the step needs no second barrier.  The
-  // pivots are Gaussian elimination's (Sc is SPD: all positive), δc_i = rc_i / a_ii at the end.
-  for (int k = 0; k < nb; ++k) {
-    const double dkk = sc[k][k];
-    if (tid == 0 && !(dkk > 0.0)) bad = 1;
-    const double idk = 1.0 / fmax(dkk, 1e-300);
-    const int m = nb - k;  // columns k + 1 … nb − 1, then rc
-    for (int idx = tid; idx < nb * m; idx += blockDim.x) {
-      const int i = idx / m, jj = idx - m * i;
-      if (i == k) continue;
-      const double f = sc[i][k] * idk;
-      if (jj < m - 1) sc[i][k + 1 + jj] -= f * sc[k][k + 1 + jj];
-      else rc[i] -= f * rc[k];
-    }
-    __syncthreads();
-  }
-  if (tid == 0 && bad) atomicOr(a.status, 2);
-  __syncthreads();
-  for (int q = tid; q < nb; q += blockDim.x) {
-    const double v = rc[q] / fmax(sc[q][q], 1e-300);
-    a.dc[q] = v;
-    a.x[6 * a.nf + q] = v;
-  }
-}
-
-// δa = X_0 − X_B δc, one lane per keyframe unknown.
-__global__ __launch_bounds__(256) void arrow_back_kernel(const ArrowArgs a) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 6 * a.nf) return;
-  const double* Xt = a.X + (long long)t * a.ldx;
-  double v = Xt[0];
-  for (int q = 0; q < 12 * a.nc; ++q) v -= Xt[1 + q] * a.dc[q];
-  a.x[t] = v;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3934,198 +2370,7 @@ int gn_lpb(const pba_engine* e) { return e->opt.residual_kind == PBA_RESIDUAL_GE
 // rows per lane of the linearisation: 1 up to 8 px (one lane per row), ⌈P/8⌉ above (linearize_adj_kernel<·, PPL>)
 int gn_ppl(const pba_engine* e) { return e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC ? 1 : (e->P + 7) / 8; }
 
-int band_kernel_for(int band) { return band <= 4 ? 4 : (band <= 8 ? 8 : (band <= 16 ? 16 : 0)); }
-
-int configure_arrow(pba_engine* e);  // (free intrinsics' arrow solve, below)
-
-// PBA_SOLVER (test hook), read on every call: the solver it forces where the system allows it
-enum class ForcedSolver { none, cr, band, skyline, front };
-ForcedSolver forced_solver() {
-  const char* fs = getenv("PBA_SOLVER");
-  if (!fs) return ForcedSolver::none;
-  const std::string f(fs);
-  return f == "cr" ? ForcedSolver::cr : f == "band" ? ForcedSolver::band : f == "skyline" ? ForcedSolver::skyline
-       : f == "front" ? ForcedSolver::front : ForcedSolver::none;
-}
-
-// Reduced-system solver buffers for band K (0: skyline only): band input Sband (row stride (K+1)·36 + 6,
-// zero outside the profile), band-Cholesky column records, cyclic-reduction levels.
-int configure_solver(pba_engine* e, int K, int solver) {
-  GnData& G = e->gn;
-  const int nf = e->n_frames;
-  hipStream_t st = e->stream;
-  G.band_kernel = K;
-  G.solver = solver;
-  G.sband_dirty = false;
-  if (K) {
-    const size_t nb_ = (size_t)nf * ((K + 1) * 36 + 6);
-    PBA_HIP(G.Lband.resize((size_t)nf * (K * 36 + 48)));  // column records
-    PBA_HIP(G.Sband.resize(nb_));
-    PBA_HIP(hipMemsetAsync(G.Sband.p, 0, nb_ * sizeof(double), st));  // positions outside the profile stay 0
-  }
-  G.cr_levels.clear();
-  G.cr_pcr = -1;
-  if (solver == SOLVER_CR) {
-    const int M = 6 * K;
-    // Parallel cyclic reduction takes over (wave kernel, M = 24) once the rows fit one workgroup per CU:
-    // PBA_PCR_CAP overrides the row limit (0: cyclic reduction only) — the tests force the hybrid with small caps
-    int cap = 0;
-    if (M == 24) {
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->opt.device) != hipSuccess) cus = 0;
-      cap = cus;
-      if (const char* v = std::getenv("PBA_PCR_CAP")) cap = std::atoi(v);
-    }
-    std::vector<int> ns{(nf + K - 1) / K};
-    while (ns.back() > (cap > 0 ? cap : 1)) ns.push_back((ns.back() + 1) / 2);
-    if (cap > 0) G.cr_pcr = (int)ns.size() - 1;
-    const int np = cap > 0 ? ns.back() : 0;
-    size_t total = 2 * ((size_t)np * M * M * 2 + (size_t)np * M);
-    for (int n : ns) total += (size_t)n * M * M * 2 + (size_t)n * M * 2 + (size_t)(n / 2) * M * (2 * M + 1);
-    PBA_HIP(G.cr_buf.resize(total));
-    size_t off = 0;
-    for (int n : ns) {
-      CrLevelHost L;
-      L.n = n;
-      L.D = off; off += (size_t)n * M * M;
-      L.U = off; off += (size_t)n * M * M;
-      L.b = off; off += (size_t)n * M;
-      L.x = off; off += (size_t)n * M;
-      L.X = off; off += (size_t)(n / 2) * M * (2 * M + 1);
-      G.cr_levels.push_back(L);
-    }
-    for (CrLevelHost& P : G.pcr_bufs) {
-      P.n = np;
-      P.D = off; off += (size_t)np * M * M;
-      P.U = off; off += (size_t)np * M * M;
-      P.b = off; off += (size_t)np * M;
-    }
-    G.cr0_dirty = true;  // level 0 is set up for assemble_kernel's direct writes on first use
-    G.cr0_inited = false;
-  }
-  return PBA_OK;
-}
-
-// The band solver for the exchange bandwidth K of a multi-GPU solve (without free intrinsics).
-int ensure_exchange_solver(pba_engine* e, int K) {
-  GnData& G = e->gn;
-  if (!G.nc_sys && (G.band_kernel != K || G.solver == SOLVER_SKYLINE)) {
-    const int solver = (K <= 8 && forced_solver() != ForcedSolver::band) ? SOLVER_CR : SOLVER_BAND;
-    if (int rc = configure_solver(e, K, solver)) return rc;
-  }
-  return PBA_OK;
-}
-
 // Symbolic analysis: GN block order, chunks, slot layouts, skyline profile and contribution lists.
-// The rows of each column's profile: column k → every i > k with first(i) ≤ k, in order (CSR).
-void profile_columns(const std::vector<int>& first, std::vector<int>& ccptr, std::vector<int>& ccrows) {
-  const int n = (int)first.size();
-  std::vector<std::vector<int>> col(n);
-  for (int i = 0; i < n; ++i)
-    for (int k = first[i]; k < i; ++k) col[k].push_back(i);
-  ccptr.assign(n + 1, 0);
-  ccrows.clear();
-  for (int k = 0; k < n; ++k) {
-    ccptr[k + 1] = ccptr[k] + (int)col[k].size();
-    ccrows.insert(ccrows.end(), col[k].begin(), col[k].end());
-  }
-  if (ccrows.empty()) ccrows.push_back(0);
-}
-
-// front_solve_kernel's plan for a skyline profile (first(i), row offsets rowp, column lists): static slots — a row
-// admitted for column k + 1 never takes a slot in use at column k — and the per-column records (see the kernel).
-// P.lds = 0 when the front does not fit (or use = false): the caller then takes skyline_solve_kernel.
-int build_front_plan(const std::vector<int>& first, const std::vector<int>& rowp, const std::vector<int>& ccptr,
-                     const std::vector<int>& ccrows, hipStream_t st, FrontPlan& P, bool use) {
-  const int nfs = (int)first.size();
-  std::vector<std::vector<int>> adm(nfs);
-  for (int i = 0; i < nfs; ++i) adm[first[i]].push_back(i);
-  std::vector<int> slot(nfs, -1), freel;
-  int F = 0;
-  auto alloc = [&]() {
-    if (freel.empty()) return F++;
-    auto it = std::min_element(freel.begin(), freel.end());
-    const int v = *it;
-    freel.erase(it);
-    return v;
-  };
-  for (int i : adm[0]) slot[i] = alloc();
-  for (int k = 0; k < nfs; ++k) {
-    if (k + 1 < nfs)
-      for (int i : adm[k + 1]) slot[i] = alloc();
-    freel.push_back(slot[k]);
-  }
-  // active set after column k's admissions: (A_k \ {k}) ∪ adm(k+1), kept sorted
-  std::vector<std::vector<int2>> fresh(nfs);  // per column k: the blocks of the rows admitted for k + 1
-  std::vector<int2> init;
-  std::vector<int> act;
-  auto blk = [&](int hi, int lo) { return rowp[hi] + (lo - first[hi]); };
-  auto add_rows = [&](const std::vector<int>& newr, std::vector<int>& A, std::vector<int2>& out) {
-    for (int i : newr) A.push_back(i);
-    std::sort(A.begin(), A.end());
-    for (int i : newr)
-      for (int j : A) {
-        if (j > i && std::binary_search(newr.begin(), newr.end(), j)) continue;  // the pair once (from j)
-        const int hi = std::max(i, j), lo = std::min(i, j);
-        out.push_back(make_int2(blk(hi, lo), slot[hi] * F + slot[lo]));
-      }
-  };
-  add_rows(adm[0], act, init);
-  int fm = 1, mf = 1;
-  for (int k = 0; k < nfs; ++k) {
-    fm = std::max(fm, ccptr[k + 1] - ccptr[k]);
-    act.erase(std::remove(act.begin(), act.end(), k), act.end());
-    if (k + 1 < nfs) add_rows(adm[k + 1], act, fresh[k]);
-    mf = std::max(mf, (int)fresh[k].size());
-  }
-  const int R = kFrontHdr + 3 * fm + 2 * mf, SB = fm * 36 + 48;
-  const size_t lds = sizeof(double) * ((size_t)F * F * 36 + 6 * (size_t)nfs + 2 * SB) +
-                     sizeof(int) * (3 * (size_t)R + fm * (fm + 1) / 2);
-  P.lds = 0;
-  if (!use || fm > 32 || mf * 36 > 256 * kFrontPf || SB > 256 * kFrontPf || R > 256 * kFrontPr || lds > 150 * 1024)
-    return PBA_OK;
-  std::vector<int> rec((size_t)nfs * R, 0);
-  for (int k = 0; k < nfs; ++k) {
-    int* r = rec.data() + (size_t)k * R;
-    const int na = ccptr[k + 1] - ccptr[k];
-    r[0] = slot[k];
-    r[1] = na;
-    r[2] = (int)fresh[k].size();
-    for (int li = 0; li < na; ++li) {
-      const int i = ccrows[ccptr[k] + li];
-      r[kFrontHdr + li] = slot[i];
-      r[kFrontHdr + fm + li] = i;
-      r[kFrontHdr + 2 * fm + li] = blk(i, k);
-    }
-    for (int q = 0; q < (int)fresh[k].size(); ++q) {
-      r[kFrontHdr + 3 * fm + q] = fresh[k][q].x;
-      r[kFrontHdr + 3 * fm + mf + q] = fresh[k][q].y;
-    }
-  }
-  PBA_HIP(P.rec.upload(rec, st));
-  P.n_init = (int)init.size();
-  if (init.empty()) init.push_back(make_int2(0, 0));
-  PBA_HIP(P.init.upload(init, st));
-  PBA_HIP(P.lrec.resize((size_t)nfs * 48));
-  P.F = F;
-  P.fm = fm;
-  P.mf = mf;
-  P.R = R;
-  P.lds = lds;
-  return PBA_OK;
-}
-
-// S δ = −g by front_solve_kernel with plan P (S: the profile's skyline blocks; L: room for its factor).
-int launch_front(pba_engine* e, FrontPlan& P, const double* S, double* L, int N) {
-  GnData& G = e->gn;
-  FrontArgs fa{S, G.g.p, L, P.lrec.p, P.rec.p, P.init.p, G.x.p, G.status.p, N, P.F, P.fm, P.mf, P.R, P.n_init};
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&front_solve_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds);  // may exceed 64 KB
-  front_solve_kernel<<<1, 256, P.lds, e->stream>>>(fa);
-  PBA_HIP(hipGetLastError());
-  return PBA_OK;
-}
-
 int gn_prepare(pba_engine* e) {
   GnData& G = e->gn;
   const int nb = e->n_blocks, nf = e->n_frames;
@@ -4532,18 +2777,7 @@ int gn_prepare(pba_engine* e) {
   PBA_HIP(G.fixed.upload(fixed, st));
   PBA_HIP(G.S.resize((size_t)G.n_sky * 36));
   PBA_HIP(G.L.resize((size_t)G.n_sky * 36));
-  // solver choice: block cyclic reduction (bandwidth ≤ 8), LDS-window band Cholesky (≤ 16), skyline (any).
-  // PBA_SOLVER=cr|band|skyline forces one (test hook; cr/band fall back when the bandwidth does not allow).
-  const int K = nc ? 0 : band_kernel_for(G.band);  // the intrinsics border: skyline
-  int solver = K && K <= 8 ? SOLVER_CR : (K ? SOLVER_BAND : SOLVER_SKYLINE);
-  const ForcedSolver f = forced_solver();
-  if (f == ForcedSolver::skyline) solver = SOLVER_SKYLINE;
-  else if (f == ForcedSolver::band && K) solver = SOLVER_BAND;
-  else if (f == ForcedSolver::cr && K && K <= 8) solver = SOLVER_CR;
-  if (int rc = configure_solver(e, solver == SOLVER_SKYLINE ? 0 : K, solver)) return rc;
-  G.ar_n = G.ar_batches = 0;  // free intrinsics: the arrow solve's buffers (arrow_for decides per solve)
-  if (nc > 0 && nc <= kArrowMaxNc)
-    if (int rc = configure_arrow(e)) return rc;
+  if (int rc = configure_local_solver(e)) return rc;
   PBA_HIP(G.observed.upload(std::vector<uint8_t>(observed.begin(), observed.end()), st));
   std::vector<uint8_t> req(nf, 0);
   for (int i = 0; i < nf && i < (int)G.fixed_h.size(); ++i) req[i] = G.fixed_h[i];
@@ -4652,188 +2886,6 @@ int linearize(pba_engine* e, double* cost, const double* lm = nullptr, const Pai
   return PBA_OK;
 }
 
-CrLevel cr_level(GnData& G, int l) {
-  const CrLevelHost& h = G.cr_levels[l];
-  double* base = G.cr_buf.p;
-  return CrLevel{base + h.D, base + h.U, base + h.b, base + h.X, base + h.x, h.n};
-}
-CrLevel pcr_level(GnData& G, int i) {  // PCR ping-pong buffer i (D, U, b of the rows of level G.cr_pcr)
-  const CrLevelHost& h = G.pcr_bufs[i];
-  double* base = G.cr_buf.p;
-  return CrLevel{base + h.D, base + h.U, base + h.b, nullptr, nullptr, h.n};
-}
-
-// Level 0 of the cyclic reduction as assemble_kernel expects it: zeros (positions outside the reduced system's profile
-// are never written), identity diagonal on the padding rows past the last keyframe.
-int init_cr_level0(pba_engine* e) {
-  GnData& G = e->gn;
-  if (G.cr_levels.empty()) return PBA_OK;
-  const int B = G.band_kernel, M = 6 * B, N = e->n_frames;
-  const CrLevelHost& h = G.cr_levels[0];
-  std::vector<double> z((size_t)h.n * M * M * 2 + (size_t)h.n * M, 0.0);  // D | U | b (contiguous: configure_solver)
-  for (int I = 0; I < h.n; ++I)
-    for (int R = 0; R < M; ++R)
-      if (I * B + R / 6 >= N) z[(size_t)I * M * M + (size_t)R * M + R] = 1.0;
-  PBA_HIP(hipMemcpyAsync(G.cr_buf.p + h.D, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
-  PBA_HIP(hipStreamSynchronize(e->stream));  // z is pageable and goes out of scope
-  G.cr0_dirty = false;
-  G.cr0_inited = true;
-  return PBA_OK;
-}
-
-// build: level 0 from Sband (cr_build_kernel); false when assemble_kernel wrote it directly
-template <int M>
-void cr_solve(pba_engine* e, bool build) {
-  GnData& G = e->gn;
-  if (cr_level_lds<M>() > 65536) {  // above the default dynamic-LDS limit (gfx950 has 160 KiB per CU)
-    // the attribute is per device: set it on every solve (cheap) rather than once per process
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cr_level_kernel<M>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)cr_level_lds<M>());
-  }
-  const int nl = (int)G.cr_levels.size();
-  CrLevel L0 = cr_level(G, 0);
-  const long long nthreads = (long long)L0.n * M * M + (long long)L0.n * M;
-  if (build)
-    cr_build_kernel<M><<<(unsigned)((nthreads + 255) / 256), 256, 0, e->stream>>>(G.Sband.p, L0, e->n_frames,
-                                                                                  G.band_kernel, G.status.p);
-  // CR levels 0 … c−1 (one fused launch each: odd eliminations + even rebuild); level c is solved either by PCR
-  // levels (G.cr_pcr = c) or, as the last CR level of one row, by the root kernel
-  const int c = G.cr_pcr >= 0 ? G.cr_pcr : nl - 1;
-  for (int l = 0; l < c; ++l) {
-    CrLevel L = cr_level(G, l), Ln = cr_level(G, l + 1);
-    if constexpr (2 * M + 1 <= 64) {
-      cr_level_wave_kernel<M, false><<<(L.n + 1) / 2, 256, cr_level_wave_lds<M>(), e->stream>>>(L, Ln, 1, G.status.p,
-                                                                                               nullptr, 0);
-    } else
-      cr_level_kernel<M><<<(L.n + 1) / 2, 2 * kCrOddThreads<M>, cr_level_lds<M>(), e->stream>>>(L, Ln, G.status.p);
-  }
-  bool solved = false;  // the step vector already written (level c = 0 solved in place)
-  if constexpr (2 * M + 1 <= 64) {
-    if (G.cr_pcr >= 0) {
-      CrLevel src = cr_level(G, c);
-      const int n = src.n;
-      solved = c == 0;
-      double* out = solved ? G.x.p : cr_level(G, c).x;
-      const int lim = solved ? 6 * e->n_frames : n * M;
-      int pi = 0;
-      for (int s = 1; s < n; s *= 2, pi ^= 1) {  // the last level also solves the decoupled rows
-        CrLevel dst = pcr_level(G, pi);
-        const bool last = 2 * s >= n;
-        cr_level_wave_kernel<M, true><<<n, 256, cr_level_wave_lds<M>(), e->stream>>>(src, dst, s, G.status.p,
-                                                                                     last ? out : nullptr, lim);
-        src = dst;
-      }
-      if (n <= 1) pcr_solve_kernel<M><<<n, 64, 0, e->stream>>>(src, out, lim, G.status.p);
-    } else {
-      cr_root_wave_kernel<M><<<1, 64, 0, e->stream>>>(cr_level(G, nl - 1), G.status.p);
-    }
-  } else {
-    cr_root_kernel<M><<<1, kCrOddThreads<M>, 0, e->stream>>>(cr_level(G, nl - 1), G.status.p);
-  }
-  if (solved) return;
-  if (c == 0) {  // a single super-row: the root's x is the step
-    (void)hipMemcpyAsync(G.x.p, L0.x, sizeof(double) * 6 * e->n_frames, hipMemcpyDeviceToDevice, e->stream);
-    return;
-  }
-  CrLevels C{};
-  C.nl = nl;
-  for (int l = 0; l < nl; ++l) C.lv[l] = cr_level(G, l);
-  int lo = c;  // the tail: levels c−1 … lo with at most kCrTailRows super-rows, in one workgroup
-  while (lo > 0 && C.lv[lo - 1].n <= kCrTailRows) --lo;
-  if (lo <= c - 1) cr_back_tail_kernel<M><<<1, 1024, 0, e->stream>>>(C, c - 1, lo, G.x.p, e->n_frames);
-  for (int l = lo - 1; l >= 0; --l) {
-    const int lim = l == 0 ? 6 * e->n_frames : C.lv[l].n * M;
-    cr_back_kernel<M><<<(lim + 255) / 256, 256, 0, e->stream>>>(C.lv[l], C.lv[l + 1].x, l == 0 ? G.x.p : C.lv[l].x, lim);
-  }
-}
-
-// Free intrinsics: the arrow solve's buffers (gn_prepare; nf keyframes, nc ≤ kArrowMaxNc cameras).
-int configure_arrow(pba_engine* e) {
-  GnData& G = e->gn;
-  constexpr int M = 24, NB = kArrowNB;
-  const int nf = e->n_frames, nc = G.nc_sys, nb = 12 * nc;
-  G.ar_n = (nf + 3) / 4;
-  G.ar_batches = (1 + nb + NB - 1) / NB;
-  // level 0: D, U (shared by the batches) and every batch's b; levels 1, 2 (ping-pong): per batch D, U, b
-  const size_t lvl = (size_t)G.ar_n * M * M * 2 + (size_t)G.ar_n * M * NB;
-  PBA_HIP(G.ar_buf.resize((size_t)G.ar_n * M * M * 2 + (size_t)G.ar_batches * (2 * lvl + (size_t)G.ar_n * M * NB)));
-  PBA_HIP(G.ar_X.resize((size_t)6 * nf * NB * G.ar_batches));
-  PBA_HIP(G.ar_part.resize((size_t)kArrowSeg * (nb * (nb + 1) / 2 + nb)));
-  PBA_HIP(G.ar_dc.resize((size_t)nb));
-  return PBA_OK;
-}
-
-// Whether a free-intrinsics system of keyframe bandwidth K is solved as an arrow (arrow_solve): K ≤ 4 (super-rows of 4
-// keyframes, M = 24), ≤ kArrowMaxNc cameras, and PBA_SOLVER does not force the skyline solvers ("skyline" / "front":
-// the A/B tests of the three solvers).
-bool arrow_for(const pba_engine* e, int K) {
-  const GnData& G = e->gn;
-  if (!G.nc_sys || G.nc_sys > kArrowMaxNc || K > 4 || !G.ar_n) return false;
-  const ForcedSolver fs = forced_solver();
-  return fs != ForcedSolver::skyline && fs != ForcedSolver::front;
-}
-
-// X = A⁻¹[−g_a | B] by parallel cyclic reduction (batches of kArrowNB columns), the border system, the step into G.x
-// (the kernels above).  S, first, row: the skyline system and its profile; fixed: the constant frames.
-// Batch 0's rows of arrow level k (configure_arrow's layout) and the arrow kernels' arguments.
-CrLevel arrow_level(const GnData& G, int k) {
-  constexpr int M = 24, NB = kArrowNB;
-  const int n = G.ar_n, nbt = G.ar_batches;
-  const size_t lvl = (size_t)n * M * M * 2 + (size_t)n * M * NB, nbq = (size_t)n * M * NB;
-  double* p = G.ar_buf.p + (k == 0 ? 0 : (size_t)n * M * M * 2 + nbt * nbq + (size_t)(k - 1) * nbt * lvl);
-  return CrLevel{p, p + (size_t)n * M * M, p + (size_t)2 * n * M * M, nullptr, nullptr, n};
-}
-ArrowArgs arrow_args(pba_engine* e, const double* S, const int* first, const int* row, const uint8_t* fixed) {
-  GnData& G = e->gn;
-  const int nb = 12 * G.nc_sys;
-  return ArrowArgs{S, first, row, G.g.p, fixed, arrow_level(G, 0), G.ar_X.p, G.ar_part.p, G.ar_dc.p, G.x.p, G.status.p,
-                   e->n_frames, G.nc_sys, kArrowNB * G.ar_batches, nb * (nb + 1) / 2 + nb};
-}
-// arrow_build's threads (level 0: D, U and every batch's right-hand sides)
-long long arrow_build_threads(const GnData& G) {
-  constexpr int M = 24;
-  return 2LL * G.ar_n * M * M + (long long)G.ar_batches * G.ar_n * M * kArrowNB;
-}
-
-// built: level 0 is already in place (intr_cam_fin_build_kernel of the same trial).
-int arrow_solve(pba_engine* e, const double* S, const int* first, const int* row, const uint8_t* fixed,
-                bool built = false) {
-  GnData& G = e->gn;
-  constexpr int M = 24, NB = kArrowNB;
-  const int nf = e->n_frames, n = G.ar_n;
-  hipStream_t st = e->stream;
-  const int nbt = G.ar_batches;
-  const size_t lvl = (size_t)n * M * M * 2 + (size_t)n * M * NB, nbq = (size_t)n * M * NB;
-  auto level = [&](int k) { return arrow_level(G, k); };
-  const ArrowArgs aa = arrow_args(e, S, first, row, fixed);
-  constexpr size_t lds = cr_level_wave_lds<M, NB>();
-  static_assert(lds <= 65536, "default dynamic LDS limit");
-  if (!built) arrow_build_kernel<<<(unsigned)((arrow_build_threads(G) + 255) / 256), 256, 0, st>>>(aa, nbt);
-  // the batches' cyclic reductions side by side (gridDim.y): one launch per level whatever the number of cameras
-  CrLevel src = level(0);
-  if (n <= 1)
-    for (int bt = 0; bt < nbt; ++bt) {
-      CrLevel sb = src;
-      sb.b += bt * nbq;
-      pcr_solve_kernel<M, NB><<<n, 64, 0, st>>>(sb, G.ar_X.p + NB * bt, 6 * nf, G.status.p, aa.ldx);
-    }
-  int pi = 1;
-  long long bs_du = 0, bs_b = (long long)nbq;  // level 0: shared D, U
-  for (int s = 1; s < n; s *= 2, pi = 3 - pi) {  // the last level also solves the decoupled rows
-    const CrLevel dst = level(pi);
-    const bool last = 2 * s >= n;
-    cr_level_wave_kernel<M, true, NB><<<dim3(n, nbt), 256, lds, st>>>(src, dst, s, G.status.p, last ? G.ar_X.p : nullptr,
-                                                                      6 * nf, aa.ldx, bs_du, bs_b, (long long)lvl);
-    src = dst;
-    bs_du = bs_b = (long long)lvl;
-  }
-  arrow_reduce_kernel<<<dim3(aa.n_ent, kArrowSeg), 256, 0, st>>>(aa);
-  arrow_cap_kernel<<<1, 256, 0, st>>>(aa);
-  arrow_back_kernel<<<(6 * nf + 255) / 256, 256, 0, st>>>(aa);
-  PBA_HIP(hipGetLastError());
-  return PBA_OK;
-}
-
 // After a solve into G.x: solver status, candidate poses/points, and the two parts of the LM model decrease
 // L(0) − L(δ) = −gᵀδ − ½δᵀHδ = ½(λ δᵀDδ − gᵀδ)  (since (H + λD)δ = −g): pose part and point part.
 // Candidate poses/points and the model-decrease partials into reduction slots [0, gp + gq) of G.red.
@@ -4882,23 +2934,6 @@ int finish_step(pba_engine* e, double lambda, const uint8_t* fixed, double* mode
   PBA_HIP(hipMemcpyAsync(G.red_h.data(), G.red.p, sizeof(double) * 2 * (gp + gq), hipMemcpyDeviceToHost, e->stream));
   PBA_HIP(hipStreamSynchronize(e->stream));
   model_from_slots(G, lambda, gp, gq, model_pose, model_points);
-  return PBA_OK;
-}
-
-// Band solvers on G.Sband (block cyclic reduction for K ≤ 8, LDS-window band Cholesky for K = 16).
-int band_solve(pba_engine* e, bool build = true) {
-  GnData& G = e->gn;
-  const int nf = e->n_frames;
-  if (G.solver == SOLVER_CR) {
-    if (G.band_kernel == 4) cr_solve<24>(e, build);
-    else cr_solve<48>(e, build);
-  } else {
-    BandArgs ba{G.Sband.p, G.Lband.p, G.x.p, G.status.p, nf};
-    if (G.band_kernel == 4) band_solve_kernel<4><<<1, 256, 0, e->stream>>>(ba);
-    else if (G.band_kernel == 8) band_solve_kernel<8><<<1, 256, 0, e->stream>>>(ba);
-    else band_solve_kernel<16><<<1, 256, 0, e->stream>>>(ba);
-  }
-  PBA_HIP(hipGetLastError());
   return PBA_OK;
 }
 
@@ -5027,12 +3062,9 @@ int enqueue_solve(pba_engine* e, double lambda, const double* lm = nullptr, bool
   if (G.band_kernel) {
     if (int rc = band_solve(e, !direct)) return rc;
   } else {
-    if (arrow) return arrow_solve(e, G.S.p, G.sky_first.p, G.sky_row.p, G.fixed.p, true);
-    if (G.front.lds) return launch_front(e, G.front, G.S.p, G.L.p, nfs);
-    PBA_HIP(hipMemcpyAsync(G.L.p, G.S.p, sizeof(double) * 36 * (size_t)G.n_sky, hipMemcpyDeviceToDevice, e->stream));
-    SolveArgs so{G.L.p, G.sky_first.p, G.sky_row.p, G.sky_last.p, G.g.p, G.Linv.p, G.x.p, G.status.p, nfs,
-                 G.sky_colptr.p, G.sky_colrows.p};
-    skyline_solve_kernel<<<1, 256, 0, e->stream>>>(so);
+    const SkylineSystem s{G.S.p, G.L.p, G.sky_first.p, G.sky_row.p, G.sky_last.p, G.sky_colptr.p, G.sky_colrows.p,
+                          G.front, G.fixed.p, nfs, G.n_sky};
+    return skyline_solve(e, s, arrow ? ArrowUse::built : ArrowUse::none);
   }
   PBA_HIP(hipGetLastError());
   return PBA_OK;
@@ -5242,14 +3274,9 @@ int enqueue_import(pba_engine* e, double lambda, const double* lm, const double*
     const long long n = ia.n_el + 6LL * nfs;
     import_sky_kernel<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(ia, lambda, lm);
     PBA_HIP(hipGetLastError());
-    if (arrow_for(e, K)) return arrow_solve(e, G.dS.p, G.dsky_first.p, G.dsky_row.p, G.fixed_dist.p);
-    if (G.dfront.lds) return launch_front(e, G.dfront, G.dS.p, G.dL.p, nfs);
-    PBA_HIP(hipMemcpyAsync(G.dL.p, G.dS.p, sizeof(double) * 36 * (size_t)G.n_dsky, hipMemcpyDeviceToDevice, e->stream));
-    SolveArgs so{G.dL.p, G.dsky_first.p, G.dsky_row.p, G.dsky_last.p, G.g.p, G.Linv.p, G.x.p, G.status.p, nfs,
-                 G.dsky_colptr.p, G.dsky_colrows.p};
-    skyline_solve_kernel<<<1, 256, 0, e->stream>>>(so);
-    PBA_HIP(hipGetLastError());
-    return PBA_OK;
+    const SkylineSystem s{G.dS.p, G.dL.p, G.dsky_first.p, G.dsky_row.p, G.dsky_last.p, G.dsky_colptr.p, G.dsky_colrows.p,
+                          G.dfront, G.fixed_dist.p, nfs, G.n_dsky};
+    return skyline_solve(e, s, arrow_for(e, K) ? ArrowUse::build : ArrowUse::none);
   }
   const bool direct = G.solver == SOLVER_CR;
   if (direct && !G.cr0_inited)  // zeros outside the band, identity padding rows

@@ -1,5 +1,5 @@
 // pba_internal.h — engine state, kernel argument blocks and the per-row residual/Jacobian arithmetic
-// shared by the Ceres-mode kernels (pba_engine.hip) and the Gauss-Newton kernels (pba_gn.hip, pba_gn_linearize.hip).
+// shared by the Ceres-mode kernels (pba_engine.hip) and the Gauss-Newton kernels (pba_gn*.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -709,7 +709,7 @@ struct CrLevelHost {
 
 // Gauss-Newton state: the symbolic analysis of the normal equations (built once per problem structure) and
 // the device buffers of one linearisation / Schur complement / solve.  See pba_gn.hip for the layouts.
-// front_solve_kernel's plan (pba_gn.hip, build_front_plan): per column k one record of kFrontHdr + 3·fm + 2·mf ints — the
+// front_solve_kernel's plan (pba_gn_solve_sky.hip, build_front_plan): per column k one record of kFrontHdr + 3·fm + 2·mf ints — the
 // slot of k, the column's row count, the fresh-block count, then the rows' slots, indices and factor blocks, then the
 // fresh blocks (source skyline block, front position) that the next column admits; the rows admitted at column 0 in init.
 struct FrontPlan {
@@ -724,7 +724,7 @@ struct GnData {
   bool prepared = false;
   int lpb = 8, bpw = 32, ppl = 1;  // linearisation: lanes per block, blocks per chunk, rows per lane
   int n_chunks = 0, n_schur = 0, n_gn_points = 0, n_sky = 0, band = 0, band_kernel = 0, solver = 0;
-  std::vector<CrLevelHost> cr_levels;  // block-cyclic-reduction level layout (offsets into cr_buf)
+  std::vector<CrLevelHost> cr_levels;  // block-cyclic-reduction level layout (offsets into cr_buf; pba_gn_solve_cr.hip)
   int cr_pcr = -1;                     // the CR level whose rows parallel cyclic reduction solves (-1: root kernel)
   CrLevelHost pcr_bufs[2];             // PCR ping-pong buffers (D, U, b) for that level's rows
   DevBuf<double> cr_buf;
@@ -783,7 +783,7 @@ struct GnData {
   DevBuf<double> dS, dL;
   DevBuf<int> dsky_row, dsky_first, dsky_last, dsky_colptr, dsky_colrows;
   int dsky_K = -1, n_dsky = 0;
-  // free intrinsics as an ARROW system (pba_gn.hip arrow_solve): the keyframe band by parallel cyclic reduction with
+  // free intrinsics as an ARROW system (pba_gn_solve_cr.hip arrow_solve): the keyframe band by parallel cyclic reduction with
   // the border's columns as extra right-hand sides, then the small dense border Schur complement.  ar_n super-rows of 4
   // keyframes, ar_batches runs of kArrowNB columns side by side; buffers: level 0 (D, U and every batch's b) + two
   // ping-pong levels (per batch D, U, b of kArrowNB columns), the solutions X (6·nf rows × 16·ar_batches), the border

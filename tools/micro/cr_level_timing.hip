@@ -1,4 +1,4 @@
-// Micro-benchmark: one cyclic-reduction level (the structure of cr_level_kernel, pba_gn.hip) on a synthetic SPD
+// Micro-benchmark: one cyclic-reduction level (the structure of cr_level_kernel, pba_gn_solve_cr.hip) on a synthetic SPD
 // block-tridiagonal level, with wall_clock64 phase stamps (load | Gauss-Jordan | products).  Diagnostic only:
 // not part of the library.  Build: hipcc -O3 --offload-arch=gfx950 -I../../photometric-bundle-adjustment_amd/csrc
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // Micro-benchmark: phase timing (s_memtime) of the Gauss-Jordan super-row elimination used by
-// cr_odd_kernel (pba_gn.hip), on a synthetic SPD level.  Diagnostic tool only; not part of the library.
+// cr_odd_kernel (pba_gn_solve_cr.hip), on a synthetic SPD level.  Diagnostic tool only; not part of the library.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>

@@ -1,6 +1,6 @@
-// Micro-benchmark: one super-row elimination of the cyclic reduction (gj_wave, pba_gn.hip) — X = D⁻¹[U | b] by a single
+// Micro-benchmark: one super-row elimination of the cyclic reduction (gj_wave, pba_gn_solve_cr.hip) — X = D⁻¹[U | b] by a single
 // wave with one lane per column, 4-column pivot blocks — in two forms:
-//   lds: the pivot columns published to LDS and read back as broadcasts (pba_gn.hip until round 5);
+//   lds: the pivot columns published to LDS and read back as broadcasts (pba_gn_solve_cr.hip until round 5);
 //   rl : the pivot columns read straight from their owner lanes' registers with v_readlane (uniform values; no LDS,
 //        no wave barriers, no pr[24][4] register block).
 // 251 workgroups of one wave (the C4 level), M = 24; per-wave cycles (s_memtime) and the launch time by events; the
@@ -58,7 +58,7 @@ __device__ __forceinline__ bool solve_pivot(double (&P)[PB][PB], double (&t)[PB]
   return bad;
 }
 
-// the round-5 form (pba_gn.hip gj_wave)
+// the round-5 form (pba_gn_solve_cr.hip gj_wave)
 __device__ __forceinline__ bool gj_lds(int c, double* piv, double* a) {
   bool bad = false;
 #pragma unroll
