@@ -128,11 +128,28 @@ int pba_record_floats(const pba_engine* engine);   /* 14·R (22·R with pba_set_
  * only at the store: ≤ 2⁻¹¹ relative per value; values beyond the half range saturate at ±65504 — at full
  * resolution a strong edge's rotation Jacobian can exceed it; the on-device GN path never reads records, it
  * accumulates JᵀJ from fp32 rows).  pba_get_records returns floats either way;
- * pba_device_records' pointer then addresses 14·R halves per block. */
+ * pba_device_records' pointer then addresses 14·R halves per block.
+ * PBA_RECORD_F16_SCALED — half records that keep the Jacobians PBA_RECORD_F16 clamps: 15·R halves per block,
+ *   [ r(R) | J_host(R×6) | J_target(R×6) | J_rho(R) | e(R) ]
+ * the first 14·R laid out as PBA_RECORD_F16, then one scale per pixel row k (a row = the 13 Jacobian values of pattern
+ * pixel k: 6 + 6 + 1); the true value of a Jacobian entry of row k is stored · e[k].  e[k] is a power of two stored as a
+ * half: with m the largest magnitude of the row's 13 fp32 values, e = 1 when m < 65520 (every value rounds to a finite
+ * half; the row is stored exactly as PBA_RECORD_F16 stores it), else e = 2^(⌊log₂ m⌋ − 14), at most 2¹⁵ — the scaled
+ * row maximum then lies in [16384, 32768).  Scaling by 1/e is exact, so the one rounding is the half conversion:
+ * ≤ 2⁻¹¹ relative per value (absolute 2⁻²⁴·e where the scaled value is a subnormal half).  Range: values beyond
+ * 65504·2¹⁵ ≈ 2.1e9 saturate at that bound.  Residuals are stored unscaled (|r| ≤ 255 for 8-bit images).  An invalid
+ * block stores 15·R zero halves; a residual-only evaluation writes only r, at the 15·R stride.  The format serves the
+ * same consumers as PBA_RECORD_F16 (AutoDiffCostFunction's Jacobian blocks of photometric_error.h:139-182 as read by
+ * ResidualBlock::Evaluate, residual_block.cc:69-158) at 30 instead of 28 bytes per row, 56 for fp32.  pba_get_records
+ * decodes on the host ((float)half · (float)e, exact), pba_decode_records_device on the device. */
 #define PBA_RECORD_F32 0
 #define PBA_RECORD_F16 1
+#define PBA_RECORD_F16_SCALED 2
 int pba_set_record_format(pba_engine* engine, int32_t format);
 int pba_record_format(const pba_engine* engine);
+/* device bytes per record as stored: 4·pba_record_floats (PBA_RECORD_F32), 28·R (PBA_RECORD_F16) or 30·R
+ * (PBA_RECORD_F16_SCALED).  pba_record_floats stays 14·R: it describes what pba_get_records returns. */
+int pba_record_bytes(const pba_engine* engine);
 /* Target-intrinsics Jacobian (geometric engines; BundleAdjustmentOptions::optimize_intrinsics, map_utils.h:339-345):
  * the reference functor takes the TARGET camera's intrinsics as its 4th parameter block (sIntr_c2, reprojection.h:83-86,
  * :108) and unprojects the host pixel with the intrinsics captured at problem build (ref_intrinsics, :93-98; Ceres never
@@ -167,11 +184,14 @@ int pba_num_frames(const pba_engine* engine);
 int pba_residuals_per_block(const pba_engine* engine);
 /* records: n_blocks·record_floats floats; valid: n_blocks bytes (either may be NULL).  Synchronises. */
 int pba_get_records(pba_engine* engine, float* records, uint8_t* valid);
+/* the record array as stored (no decoding): n_blocks·pba_record_bytes bytes into dst, `bytes` = dst's capacity —
+ * fp32 values, halves, or the 15·R-half records of PBA_RECORD_F16_SCALED.  Synchronises. */
+int pba_get_records_raw(pba_engine* engine, void* dst, size_t bytes);
 /* residuals only: n_blocks·R floats (the first R values of every record, one strided DMA copy instead of the
  * whole record — what a residual-only evaluation needs, trust_region_minimizer.cc:761-779); valid may be NULL.
  * Synchronises. */
 int pba_get_residuals(pba_engine* engine, float* residuals, uint8_t* valid);
-/* Asynchronous read-back in chunks (fp32 records): enqueues the copies of records and validity into caller-owned
+/* Asynchronous read-back in chunks (fp32 records only: PBA_RECORD_F16 and PBA_RECORD_F16_SCALED are refused): enqueues the copies of records and validity into caller-owned
  * page-locked memory behind the evaluation, chunk_blocks blocks per copy, and returns at once; pba_wait_records returns
  * once the chunk holding `block` has arrived.  Thread-safe for concurrent waiters (Ceres' evaluator threads), so the
  * per-block CostFunction::Evaluate work overlaps the transfer of later chunks (program_evaluator.h:187-258). */
@@ -190,7 +210,14 @@ int pba_get_cost(pba_engine* engine, double* total_cost, int32_t* n_valid);
 /* hipStream_t the engine enqueues on (may be replaced with pba_set_stream; NULL = engine's own) */
 int pba_set_stream(pba_engine* engine, void* hip_stream);
 int pba_get_stream(pba_engine* engine, void** hip_stream);
+/* d_records addresses the records as stored, pba_record_bytes per block: floats, 14·R halves (PBA_RECORD_F16) or the
+ * 15·R halves [r | J_host | J_target | J_rho | e] of PBA_RECORD_F16_SCALED */
 int pba_device_records(pba_engine* engine, float** d_records, uint8_t** d_valid, float** d_costs);
+/* Expand the engine's records, in any format, to n_blocks·pba_record_floats fp32 values at d_out (device memory; 16-B
+ * stores when it is 16-B aligned, 4-B stores otherwise): a copy for PBA_RECORD_F32, half → float for PBA_RECORD_F16, (float)half · (float)e for
+ * PBA_RECORD_F16_SCALED — the values pba_get_records returns.  Enqueued on the engine's stream, for in-process
+ * consumers of pba_device_records that want the fp32 Jacobian blocks of residual_block.cc:69-158. */
+int pba_decode_records_device(pba_engine* engine, float* d_out);
 
 /* Kernel timing: when enabled, every pba_evaluate brackets its residual/Jacobian block kernel with
  * hipEvents on the engine stream; pba_get_kernel_timing synchronises, returns the summed device time of

@@ -130,6 +130,22 @@ __device__ __forceinline__ _Float16 rec_val<_Float16>(float v) {
   return (_Float16)(isnan(v) ? v : __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f));
 }
 
+// Storage tag of PBA_RECORD_F16_SCALED: halves with one power-of-two scale per pixel row, 15 halves per row
+// ([r | J_host | J_target | J_rho | e], pba.h).  RecFormat<T>: what a kernel stores (S) and a record's columns per row.
+struct ScaledF16 {};
+template <class T>
+struct RecFormat {
+  using S = T;
+  static constexpr int kCols = 14;
+  static constexpr bool kScaled = false;
+};
+template <>
+struct RecFormat<ScaledF16> {
+  using S = _Float16;
+  static constexpr int kCols = 15;
+  static constexpr bool kScaled = true;
+};
+
 // Store a workgroup's contiguous record slab (LDS → global): 16-B non-temporal stores when the slab is 16-B
 // aligned, 4-B or 2-B stores otherwise (odd patterns in fp16).
 // wt (wave-uniform, KernelArgs::slab_wt): non-temporal write-through stores (`nt sc1`) — for launches of at most one
@@ -162,23 +178,85 @@ __device__ __forceinline__ void store_slab(const unsigned char* src, unsigned ch
   }
 }
 
-template <int PM, int LPB, int MODE, class T>  // PM = camera model + 4 · interpolator
+typedef float rec_f2 __attribute__((ext_vector_type(2)));
+typedef _Float16 rec_h2 __attribute__((ext_vector_type(2)));
+
+// Row px of a half record into its LDS stage: c = {r, J_rho}, 3 × J_host pairs, 3 × J_target pairs.  The 6-value rows
+// as 4-byte LDS writes where they are 4-byte aligned (LDS issue is what the 21-px kernel waits on: SQ_WAIT_INST_LDS
+// ≈ 0.26 of wave time): 3 per row when `even` (the J_host row starts on a 4-byte boundary), else 1 + 2 + 1 with the
+// inner pairs re-packed.
+__device__ __forceinline__ void stage_halves(_Float16* s_rec, int P, int px, const rec_h2 (&c)[7], bool even) {
+  _Float16* h = s_rec + P + 6 * px;
+  _Float16* t = s_rec + 7 * P + 6 * px;
+  s_rec[px] = c[0].x;
+  s_rec[13 * P + px] = c[0].y;
+  if (even) {
+    rec_h2* h4 = reinterpret_cast<rec_h2*>(h);
+    rec_h2* t4 = reinterpret_cast<rec_h2*>(t);
+    h4[0] = c[1]; h4[1] = c[2]; h4[2] = c[3];
+    t4[0] = c[4]; t4[1] = c[5]; t4[2] = c[6];
+  } else {
+    rec_h2* h4 = reinterpret_cast<rec_h2*>(h + 1);
+    rec_h2* t4 = reinterpret_cast<rec_h2*>(t + 1);
+    h[0] = c[1].x; h4[0] = (rec_h2){c[1].y, c[2].x}; h4[1] = (rec_h2){c[2].y, c[3].x}; h[5] = c[3].y;
+    t[0] = c[4].x; t4[0] = (rec_h2){c[4].y, c[5].x}; t4[1] = (rec_h2){c[5].y, c[6].x}; t[5] = c[6].y;
+  }
+}
+
+// Row px of a PBA_RECORD_F16_SCALED record (pba.h), by the lane that evaluated it: with m the largest magnitude of the
+// row's 13 Jacobian values, e = 1 for m < 65520 (every value rounds to a finite half: the row is stored as
+// PBA_RECORD_F16 stores it), else e = 2^(⌊log₂ m⌋ − 14) ≤ 2¹⁵, which puts the scaled maximum into [16384, 32768).  The
+// multiplication by 1/e is exact, so the one rounding is the half conversion.  Beyond 65504·2¹⁵ the scaled values
+// saturate at ±65504.  The residual is not scaled.  s_rec is block lb's record in the 4-byte aligned stage (15·P halves per
+// block: an odd P puts every other block on a 2-byte boundary).
+__device__ __forceinline__ void stage_row_scaled(_Float16* s_rec, int lb, int P, int px, const Row& row, bool act) {
+  const float j[13] = {row.jr, row.hv.x, row.hv.y, row.hv.z, row.hw.x, row.hw.y, row.hw.z,
+                       row.tv.x, row.tv.y, row.tv.z, row.tw.x, row.tw.y, row.tw.z};
+  float m = 0.0f;  // (a NaN drops out of the max and stays NaN in the record)
+#pragma unroll
+  for (int q = 0; q < 13; ++q) m = fmaxf(m, fabsf(j[q]));
+  int ex = 0;  // e = 2^ex
+  if (m >= 65520.0f) ex = min((int)((__float_as_uint(m) >> 23) & 0xffu) - (127 + 14), 15);  // (m = +inf: the cap)
+  const float inv = __uint_as_float((unsigned)(127 - ex) << 23);
+  // the residual saturates as PBA_RECORD_F16's does (|r| ≤ 255 for 8-bit images)
+  const float r = isnan(row.r) ? row.r : __builtin_amdgcn_fmed3f(row.r, -65504.0f, 65504.0f);
+  rec_h2 c[7];
+  c[0] = __builtin_convertvector((rec_f2){r, j[0] * inv}, rec_h2);
+#pragma unroll
+  for (int q = 1; q < 7; ++q) c[q] = __builtin_convertvector((rec_f2){j[2 * q - 1] * inv, j[2 * q] * inv}, rec_h2);
+  if (ex == 15) {  // the largest scale: a value beyond the format's range rounded to ±inf and saturates
+    auto sat = [](_Float16 h) -> _Float16 {
+      return __builtin_isinf(h) ? (h > (_Float16)0 ? (_Float16)65504.0f : (_Float16)-65504.0f) : h;
+    };
+    c[0].y = sat(c[0].y);
+#pragma unroll
+    for (int q = 1; q < 7; ++q) c[q] = (rec_h2){sat(c[q].x), sat(c[q].y)};
+  }
+  if (act) {
+    stage_halves(s_rec, P, px, c, ((lb + 1) & P & 1) == 0);  // J_host row at half (15·lb + 1)·P + 6·px of the stage
+    reinterpret_cast<unsigned short*>(s_rec)[14 * P + px] = (unsigned short)((15 + ex) << 10);  // 2^ex as a half
+  }
+}
+
+template <int PM, int LPB, int MODE, class T>  // PM = camera model + 4 · interpolator; T = float, _Float16 or ScaledF16
 __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const KernelArgs a) {
   constexpr int BPW = kBlockThreads / LPB;  // blocks per workgroup
   constexpr bool JAC = MODE == 1;
-  constexpr int kStageBytes = JAC ? BPW * 14 * LPB * (int)sizeof(T) : 0;
+  using S = typename RecFormat<T>::S;  // the stored type
+  constexpr int kCols = RecFormat<T>::kCols;
+  constexpr int kStageBytes = JAC ? BPW * kCols * LPB * (int)sizeof(S) : 0;
   constexpr int kTileBytes = BPW * (int)sizeof(TileBlock);
   __shared__ __attribute__((aligned(16))) unsigned char lds[kStageBytes > kTileBytes ? kStageBytes : kTileBytes];
   TileBlock* s_tb = reinterpret_cast<TileBlock*>(lds);
   const int P = a.P;
-  const int rec_f = 14 * P;
+  const int rec_f = kCols * P;
   const int blk0 = logical_tile() * BPW;
   const int lb = threadIdx.x / LPB;
   const int k = threadIdx.x % LPB;
   const int blk = blk0 + lb;
   const bool live = blk < a.n_blocks;  // a block's LPB lanes agree
   const bool act = live && k < P;
-  T* out = reinterpret_cast<T*>(a.out);  // records in the engine's format (fp32, or fp16 for PBA_RECORD_F16)
+  S* out = reinterpret_cast<S*>(a.out);  // records in the engine's format (fp32, or halves: PBA_RECORD_F16 / _SCALED)
 
   const float2 off = pattern_at<LPB>(a, k);
   adopt_state(a);
@@ -210,35 +288,42 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
   }
   if (!JAC) {
     if (act) {
-      out[(long long)blk * rec_f + k] = rec_val<T>(ok ? row.r : 0.0f);
+      out[(long long)blk * rec_f + k] = rec_val<S>(ok ? row.r : 0.0f);
       if (a.res_out) a.res_out[(long long)blk * P + k] = ok ? row.r : 0.0f;  // contiguous: one D2H copy for Ceres
     }
     return;
   }
   __syncthreads();  // every lane has read its tile block: the record stage may overwrite it
-  T* stage = reinterpret_cast<T*>(lds);
+  S* stage = reinterpret_cast<S*>(lds);
   // stage the record row of pixel k: r | J_host row | J_target row | J_rho  (zeros for invalid blocks)
-  if (act) {
-    T* s_rec = stage + lb * rec_f;
-    T* h = s_rec + P + 6 * k;
-    T* t = s_rec + 7 * P + 6 * k;
+  if constexpr (RecFormat<T>::kScaled) {  // … | e, the row's scale
+    S* s_rec = stage + lb * rec_f;
+    stage_row_scaled(s_rec, lb, P, k, row, act && ok);
+    if (act && !ok) {
+      s_rec[k] = s_rec[13 * P + k] = s_rec[14 * P + k] = (S)0.0f;
+      for (int j = 0; j < 6; ++j) s_rec[P + 6 * k + j] = s_rec[7 * P + 6 * k + j] = (S)0.0f;
+    }
+  } else if (act) {
+    S* s_rec = stage + lb * rec_f;
+    S* h = s_rec + P + 6 * k;
+    S* t = s_rec + 7 * P + 6 * k;
     if (ok) {
-      s_rec[k] = rec_val<T>(row.r);
-      h[0] = rec_val<T>(row.hv.x); h[1] = rec_val<T>(row.hv.y); h[2] = rec_val<T>(row.hv.z);
-      h[3] = rec_val<T>(row.hw.x); h[4] = rec_val<T>(row.hw.y); h[5] = rec_val<T>(row.hw.z);
-      t[0] = rec_val<T>(row.tv.x); t[1] = rec_val<T>(row.tv.y); t[2] = rec_val<T>(row.tv.z);
-      t[3] = rec_val<T>(row.tw.x); t[4] = rec_val<T>(row.tw.y); t[5] = rec_val<T>(row.tw.z);
-      s_rec[13 * P + k] = rec_val<T>(row.jr);
+      s_rec[k] = rec_val<S>(row.r);
+      h[0] = rec_val<S>(row.hv.x); h[1] = rec_val<S>(row.hv.y); h[2] = rec_val<S>(row.hv.z);
+      h[3] = rec_val<S>(row.hw.x); h[4] = rec_val<S>(row.hw.y); h[5] = rec_val<S>(row.hw.z);
+      t[0] = rec_val<S>(row.tv.x); t[1] = rec_val<S>(row.tv.y); t[2] = rec_val<S>(row.tv.z);
+      t[3] = rec_val<S>(row.tw.x); t[4] = rec_val<S>(row.tw.y); t[5] = rec_val<S>(row.tw.z);
+      s_rec[13 * P + k] = rec_val<S>(row.jr);
     } else {
-      s_rec[k] = (T)0.0f;
-      for (int j = 0; j < 6; ++j) h[j] = t[j] = (T)0.0f;
-      s_rec[13 * P + k] = (T)0.0f;
+      s_rec[k] = (S)0.0f;
+      for (int j = 0; j < 6; ++j) h[j] = t[j] = (S)0.0f;
+      s_rec[13 * P + k] = (S)0.0f;
     }
   }
   __syncthreads();
   const int nblk = min(BPW, a.n_blocks - blk0);
   if (nblk <= 0) return;
-  store_slab<T>(lds, reinterpret_cast<unsigned char*>(out + (long long)blk0 * rec_f), nblk * rec_f * (int)sizeof(T),
+  store_slab<S>(lds, reinterpret_cast<unsigned char*>(out + (long long)blk0 * rec_f), nblk * rec_f * (int)sizeof(S),
                 a.slab_wt);
 }
 
@@ -250,8 +335,8 @@ __device__ __forceinline__ void stage_row(T* s_rec, int P, int px, const Row& ro
     // fp16 records: the 14 values in 7 packed round-to-nearest conversions (v_cvt_pk_f16_f32) instead of a
     // NaN-preserving clamp + conversion each; a value beyond the half range rounds to ±inf there, which rec_val
     // saturates to ±65504 — applied afterwards, only when some lane of the wave has one (a ballot)
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    typedef rec_f2 f2;
+    typedef rec_h2 h2;
     const float v[14] = {row.r, row.jr, row.hv.x, row.hv.y, row.hv.z, row.hw.x, row.hw.y, row.hw.z,
                          row.tv.x, row.tv.y, row.tv.z, row.tw.x, row.tw.y, row.tw.z};
     h2 c[7];
@@ -271,25 +356,8 @@ __device__ __forceinline__ void stage_row(T* s_rec, int P, int px, const Row& ro
 #pragma unroll
       for (int q = 0; q < 7; ++q) c[q] = (h2){sat(c[q].x), sat(c[q].y)};
     }
-    if (act) {
-      // the 6-value rows as 4-byte LDS writes where they are 4-byte aligned (LDS issue is what this kernel waits on:
-      // SQ_WAIT_INST_LDS ≈ 0.26 of wave time): 3 per row for even P, 1 + 2 + 1 for odd P (the inner pairs re-packed)
-      T* h = s_rec + P + 6 * px;
-      T* t = s_rec + 7 * P + 6 * px;
-      s_rec[px] = c[0].x;
-      s_rec[13 * P + px] = c[0].y;
-      if ((P & 1) == 0) {
-        h2* h4 = reinterpret_cast<h2*>(h);
-        h2* t4 = reinterpret_cast<h2*>(t);
-        h4[0] = c[1]; h4[1] = c[2]; h4[2] = c[3];
-        t4[0] = c[4]; t4[1] = c[5]; t4[2] = c[6];
-      } else {
-        h2* h4 = reinterpret_cast<h2*>(h + 1);
-        h2* t4 = reinterpret_cast<h2*>(t + 1);
-        h[0] = c[1].x; h4[0] = (h2){c[1].y, c[2].x}; h4[1] = (h2){c[2].y, c[3].x}; h[5] = c[3].y;
-        t[0] = c[4].x; t4[0] = (h2){c[4].y, c[5].x}; t4[1] = (h2){c[5].y, c[6].x}; t[5] = c[6].y;
-      }
-    }
+    // (14·P halves per block: the J_host row starts on a 4-byte boundary for even P)
+    if (act) stage_halves(s_rec, P, px, c, (P & 1) == 0);
   } else if (act) {  // record row px: r | J_host row | J_target row | J_rho
     T* h = s_rec + P + 6 * px;
     T* t = s_rec + 7 * P + 6 * px;
@@ -309,18 +377,28 @@ __device__ __forceinline__ void stage_row(T* s_rec, int P, int px, const Row& ro
 // produced (stage and tile in separate LDS regions); an invalid block's record is zeroed once its validity is known
 // (the same lanes rewrite their own rows: LDS operations of one wave stay in order).  256 threads per workgroup,
 // 128 when the fp32 stage of 32 blocks would not fit the 64 KiB of static LDS.
-__host__ __device__ constexpr int multi_stage_bytes(int bpw, int P, int tsize) { return (bpw * 14 * P * tsize + 15) & ~15; }
+__host__ __device__ constexpr int multi_stage_bytes(int bpw, int P, int tsize, int cols = 14) {
+  return (bpw * cols * P * tsize + 15) & ~15;
+}
 
 template <int PPL, class T>
-constexpr int kMultiThreads = 32 * 14 * 8 * PPL * (int)sizeof(T) + 32 * (int)sizeof(TileBlock) > 60 * 1024 ? 128 : 256;
+constexpr int kMultiThreads = 32 * RecFormat<T>::kCols * 8 * PPL * (int)sizeof(typename RecFormat<T>::S) +
+                                          32 * (int)sizeof(TileBlock) > 60 * 1024 ? 128 : 256;
 
 // CT: the camera-table form (fused state, ≤ kCamTab cameras, 256 threads): compact 192-B tile blocks plus one LDS
 // CamRec per camera instead of 352-B tile blocks carrying both cameras (the 21-px fp16 launch: 30.1 → 25.6 KB of LDS
 // per workgroup, 5 → 6 workgroups per CU, which its 78 VGPRs also allow).
 // C1 (with CT, one camera): the rows take the camera constants from scalar loads of the engine's camera record instead
 // of the LDS table (no per-row LDS reads of them, no VGPRs).
+// kMultiWaves: the waves per SIMD the camera-table form is compiled for.  6, except the scaled-half records of 9–16 and
+// 25–32 px: held to 80 VGPRs those spilled 8–28 B per lane, and six workgroups are out of reach of the 25–32-px stage
+// anyway (15 halves per row: 30.7 KB of stage per workgroup, 4 per CU).
+template <int PPL, class T>
+constexpr int kMultiWaves = RecFormat<T>::kScaled && PPL != 3 ? 5 : 6;
+
 template <int PM, int MODE, class T, int PPL, bool CT = false, bool C1 = false>
-__global__ __launch_bounds__((kMultiThreads<PPL, T>)) __attribute__((amdgpu_waves_per_eu(CT ? 6 : 1, 8)))
+__global__ __launch_bounds__((kMultiThreads<PPL, T>))
+__attribute__((amdgpu_waves_per_eu(CT ? (kMultiWaves<PPL, T>) : 1, 8)))
 void photometric_block_kernel_multi(const KernelArgs a) {
   constexpr int LPB = 8, NTH = kMultiThreads<PPL, T>, BPW = NTH / LPB;
   constexpr bool JAC = MODE == 1;
@@ -331,16 +409,18 @@ void photometric_block_kernel_multi(const KernelArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   __shared__ float2 s_pat[LPB * PPL];
   __shared__ CamRec s_cam[CT ? kCamTab : 1];
+  using S = typename RecFormat<T>::S;  // the stored type
+  constexpr int kCols = RecFormat<T>::kCols;
   const int P = a.P;
-  T* stage = reinterpret_cast<T*>(lds);
-  TB* s_tb = reinterpret_cast<TB*>(lds + (JAC ? multi_stage_bytes(BPW, P, (int)sizeof(T)) : 0));
-  const int rec_f = 14 * P;
+  S* stage = reinterpret_cast<S*>(lds);
+  TB* s_tb = reinterpret_cast<TB*>(lds + (JAC ? multi_stage_bytes(BPW, P, (int)sizeof(S), kCols) : 0));
+  const int rec_f = kCols * P;
   const int blk0 = logical_tile() * BPW;
   const int lb = threadIdx.x / LPB;
   const int k = threadIdx.x % LPB;
   const int blk = blk0 + lb;
   const bool live = blk < a.n_blocks;  // a block's LPB lanes agree
-  T* out = reinterpret_cast<T*>(a.out);
+  S* out = reinterpret_cast<S*>(a.out);
 
   if ((int)threadIdx.x < LPB * PPL) s_pat[threadIdx.x] = pattern_at<LPB * PPL>(a, threadIdx.x);
   adopt_state(a);
@@ -361,7 +441,7 @@ void photometric_block_kernel_multi(const KernelArgs a) {
     Ih[j] = live && px < P ? a.host_int[(long long)pt * P + px] : 0.0f;
   }
   __syncthreads();
-  T* s_rec = stage + lb * rec_f;
+  S* s_rec = stage + lb * rec_f;
   int okl = 1;
   float s = 0.0f, rr[PPL];
   auto pixel = [&](int j, float ih) {
@@ -370,7 +450,8 @@ void photometric_block_kernel_multi(const KernelArgs a) {
     const Row row = photometric_row<PM, JAC, TB, C1>(a, s_tb[lb], s_pat[px < P ? px : 0], ih, s_cam);  // masked by act
     okl &= act ? row.ok : 1;
     s += act ? row.r * row.r : 0.0f;
-    if constexpr (JAC) stage_row<T>(s_rec, P, px, row, act);
+    if constexpr (JAC && RecFormat<T>::kScaled) stage_row_scaled(s_rec, lb, P, px, row, act);
+    else if constexpr (JAC) stage_row<S>(s_rec, P, px, row, act);
     return row.r;
   };
   if constexpr (JAC) {
@@ -410,7 +491,7 @@ void photometric_block_kernel_multi(const KernelArgs a) {
     for (int j = 0; j < PPL; ++j) {
       const int px = k + LPB * j;
       if (live && px < P) {
-        out[(long long)blk * rec_f + px] = rec_val<T>(ok ? rr[j] : 0.0f);
+        out[(long long)blk * rec_f + px] = rec_val<S>(ok ? rr[j] : 0.0f);
         if (a.res_out) a.res_out[(long long)blk * P + px] = ok ? rr[j] : 0.0f;
       }
     }
@@ -421,15 +502,16 @@ void photometric_block_kernel_multi(const KernelArgs a) {
     for (int j = 0; j < PPL; ++j) {
       const int px = k + LPB * j;
       if (px >= P) continue;
-      s_rec[px] = (T)0.0f;
-      s_rec[13 * P + px] = (T)0.0f;
-      for (int q = 0; q < 6; ++q) s_rec[P + 6 * px + q] = s_rec[7 * P + 6 * px + q] = (T)0.0f;
+      s_rec[px] = (S)0.0f;
+      s_rec[13 * P + px] = (S)0.0f;
+      for (int q = 0; q < 6; ++q) s_rec[P + 6 * px + q] = s_rec[7 * P + 6 * px + q] = (S)0.0f;
+      if constexpr (kCols == 15) s_rec[14 * P + px] = (S)0.0f;
     }
   }
   __syncthreads();
   const int nblk = min(BPW, a.n_blocks - blk0);
   if (nblk <= 0) return;
-  store_slab<T, NTH>(lds, reinterpret_cast<unsigned char*>(out + (long long)blk0 * rec_f), nblk * rec_f * (int)sizeof(T));
+  store_slab<S, NTH>(lds, reinterpret_cast<unsigned char*>(out + (long long)blk0 * rec_f), nblk * rec_f * (int)sizeof(S));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -518,6 +600,51 @@ __global__ __launch_bounds__(kBlockThreads) void geometric_block_kernel(const Ke
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Record decode (pba_decode_records_device): half records → 14·P floats per block.  A workgroup takes kDecodeBlocks
+// blocks: their contiguous half records into LDS by 16-B loads (32 records start on a 64-B boundary of the engine's
+// record array), then 4 consecutive output values per lane as one 16-B store.  cols = 14 (PBA_RECORD_F16: a plain
+// conversion) or 15 (PBA_RECORD_F16_SCALED: a Jacobian entry of pixel row k times the row's scale e[k], exact).
+// ------------------------------------------------------------------------------------------------
+constexpr int kDecodeBlocks = 32;
+
+__global__ __launch_bounds__(kBlockThreads) void decode_records_kernel(const _Float16* __restrict__ in,
+                                                                        float* __restrict__ out, int n_blocks, int P,
+                                                                        int cols) {
+  __shared__ __attribute__((aligned(16))) _Float16 s[kDecodeBlocks * 15 * PBA_MAX_PATTERN];
+  const int b0 = blockIdx.x * kDecodeBlocks;
+  const int nb = min(kDecodeBlocks, n_blocks - b0);
+  const int rec_i = cols * P, rec_o = 14 * P;
+  const int n_in = nb * rec_i, n_out = nb * rec_o;
+  const _Float16* src = in + (long long)b0 * rec_i;
+  {
+    const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
+    f32x4* d4 = reinterpret_cast<f32x4*>(s);
+    for (int i = threadIdx.x; i < (n_in >> 3); i += kBlockThreads) d4[i] = __builtin_nontemporal_load(s4 + i);
+    for (int i = (n_in & ~7) + threadIdx.x; i < n_in; i += kBlockThreads) s[i] = src[i];
+  }
+  __syncthreads();
+  auto value = [&](int o) -> float {
+    const int b = o / rec_o, c = o - b * rec_o;
+    const _Float16* r = s + b * rec_i;
+    float v = (float)r[c];
+    if (cols == 15 && c >= P) {  // column c of [r | J_host (P×6) | J_target (P×6) | J_rho (P)] belongs to pixel row:
+      const int row = c < 13 * P ? ((c - P) % (6 * P)) / 6 : c - 13 * P;
+      v *= (float)r[14 * P + row];
+    }
+    return v;
+  };
+  float* dst = out + (long long)b0 * rec_o;
+  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+    f32x4* d4 = reinterpret_cast<f32x4*>(dst);
+    for (int i = threadIdx.x; i < (n_out >> 2); i += kBlockThreads)
+      __builtin_nontemporal_store(f32x4{value(4 * i), value(4 * i + 1), value(4 * i + 2), value(4 * i + 3)}, d4 + i);
+    for (int i = (n_out & ~3) + threadIdx.x; i < n_out; i += kBlockThreads) dst[i] = value(i);
+  } else {
+    for (int i = threadIdx.x; i < n_out; i += kBlockThreads) dst[i] = value(i);
+  }
+}
+
 template <int MODEL>
 void launch_geometric(pba_engine* e, const KernelArgs& ka, int mode) {
   const int grid = (e->n_blocks + kBlockThreads - 1) / kBlockThreads;
@@ -531,12 +658,14 @@ void launch_geometric(pba_engine* e, const KernelArgs& ka, int mode) {
 // PM = camera model + 4 · interpolator (pba_device.h)
 template <int PM>
 void launch_photometric(pba_engine* e, KernelArgs ka, int mode) {
-  const bool h = e->record_format == PBA_RECORD_F16;
+  const bool h = e->record_format == PBA_RECORD_F16, hs = e->record_format == PBA_RECORD_F16_SCALED;
   if (e->P <= 8) {
     const int grid = (int)(((long long)e->n_blocks * 8 + kBlockThreads - 1) / kBlockThreads);
     e->last_grid = grid;
     ka.slab_wt = grid <= kSlabWtGrid;  // one wave of workgroups: write-through record stores (store_slab)
-    if (mode == 1 && h) photometric_block_kernel<PM, 8, 1, _Float16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    if (mode == 1 && hs) photometric_block_kernel<PM, 8, 1, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    else if (mode == 0 && hs) photometric_block_kernel<PM, 8, 0, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    else if (mode == 1 && h) photometric_block_kernel<PM, 8, 1, _Float16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 1) photometric_block_kernel<PM, 8, 1, float><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 0 && h) photometric_block_kernel<PM, 8, 0, _Float16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 0) photometric_block_kernel<PM, 8, 0, float><<<grid, kBlockThreads, 0, e->stream>>>(ka);
@@ -551,7 +680,8 @@ void launch_photometric(pba_engine* e, KernelArgs ka, int mode) {
     constexpr int nth = kMultiThreads<PPL, TT>;                                                         \
     const int grid = (int)(((long long)e->n_blocks * 8 + nth - 1) / nth);                              \
     e->last_grid = grid;                                                                                \
-    const size_t stage = M == 1 ? multi_stage_bytes(nth / 8, e->P, (int)sizeof(TT)) : 0;               \
+    const size_t stage = M == 1 ? multi_stage_bytes(nth / 8, e->P, (int)sizeof(RecFormat<TT>::S),      \
+                                                    RecFormat<TT>::kCols) : 0;                         \
     if (M == 1 && nth == 256 && ct && ka.n_cams == 1) {                                                 \
       photometric_block_kernel_multi<PM, M, TT, PPL, (M == 1 && nth == 256), (M == 1 && nth == 256)>    \
           <<<grid, nth, stage + (size_t)(nth / 8) * sizeof(TileBlockC), e->stream>>>(ka);              \
@@ -564,7 +694,9 @@ void launch_photometric(pba_engine* e, KernelArgs ka, int mode) {
     }                                                                                                   \
   }
 #define PBA_LAUNCH_PPL(PPL)                                        \
-  if (mode == 1 && h) PBA_LAUNCH_ONE(PPL, 1, _Float16)             \
+  if (mode == 1 && hs) PBA_LAUNCH_ONE(PPL, 1, ScaledF16)           \
+  else if (mode == 0 && hs) PBA_LAUNCH_ONE(PPL, 0, ScaledF16)      \
+  else if (mode == 1 && h) PBA_LAUNCH_ONE(PPL, 1, _Float16)        \
   else if (mode == 1) PBA_LAUNCH_ONE(PPL, 1, float)                \
   else if (mode == 0 && h) PBA_LAUNCH_ONE(PPL, 0, _Float16)        \
   else if (mode == 0) PBA_LAUNCH_ONE(PPL, 0, float)                \
@@ -1152,8 +1284,9 @@ int pba_record_floats(const pba_engine* e) { return e ? e->rec_floats() : 0; }
 
 int pba_set_record_format(pba_engine* e, int32_t format) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
-  if (format != PBA_RECORD_F32 && format != PBA_RECORD_F16) return fail(PBA_ERR_INVALID_ARGUMENT, "unknown record format");
-  if (format == PBA_RECORD_F16 && e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC)
+  if (format != PBA_RECORD_F32 && format != PBA_RECORD_F16 && format != PBA_RECORD_F16_SCALED)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "unknown record format");
+  if (format != PBA_RECORD_F32 && e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC)
     return fail(PBA_ERR_INVALID_ARGUMENT, "fp16 records are photometric only");
   e->record_format = format;
   e->evaluated = false;
@@ -1162,6 +1295,7 @@ int pba_set_record_format(pba_engine* e, int32_t format) {
 }
 
 int pba_record_format(const pba_engine* e) { return e ? e->record_format : PBA_RECORD_F32; }
+int pba_record_bytes(const pba_engine* e) { return e ? e->rec_bytes() : 0; }
 int pba_residuals_per_block(const pba_engine* e) { return e ? e->R() : 0; }
 int pba_num_blocks(const pba_engine* e) { return e ? e->n_blocks : 0; }
 int pba_num_points(const pba_engine* e) { return e ? e->n_points : 0; }
@@ -1172,16 +1306,45 @@ int pba_get_records(pba_engine* e, float* records, uint8_t* valid) {
   if (!e->evaluated) return fail(PBA_ERR_NOT_READY, "pba_evaluate first");
   if (int rc = check_device(e)) return rc;
   const size_t n = (size_t)e->n_blocks * e->rec_floats();
+  const bool scaled = e->record_format == PBA_RECORD_F16_SCALED;
   std::vector<_Float16> half;
-  if (records && e->record_format == PBA_RECORD_F16) {
-    half.resize(n);
-    PBA_HIP(hipMemcpyAsync(half.data(), e->out.p, n * sizeof(_Float16), hipMemcpyDeviceToHost, e->stream));
+  if (records && e->record_format != PBA_RECORD_F32) {
+    half.resize((size_t)e->n_blocks * e->rec_bytes() / sizeof(_Float16));
+    PBA_HIP(hipMemcpyAsync(half.data(), e->out.p, half.size() * sizeof(_Float16), hipMemcpyDeviceToHost, e->stream));
   } else if (records) {
     PBA_HIP(hipMemcpyAsync(records, e->out.p, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
   }
   if (valid) PBA_HIP(hipMemcpyAsync(valid, e->valid.p, e->n_blocks, hipMemcpyDeviceToHost, e->stream));
   PBA_HIP(hipStreamSynchronize(e->stream));
-  for (size_t i = 0; i < half.size(); ++i) records[i] = (float)half[i];
+  if (scaled && records) {  // [r | J_host | J_target | J_rho | e]: a Jacobian entry of pixel row k is stored · e[k]
+    const size_t R = (size_t)e->R();
+    for (size_t b = 0; b < (size_t)e->n_blocks; ++b) {
+      const _Float16* s = half.data() + b * 15 * R;
+      float* d = records + b * 14 * R;
+      for (size_t k = 0; k < R; ++k) {
+        const float sc = (float)s[14 * R + k];
+        d[k] = (float)s[k];
+        for (size_t j = 0; j < 6; ++j) {
+          d[R + 6 * k + j] = (float)s[R + 6 * k + j] * sc;
+          d[7 * R + 6 * k + j] = (float)s[7 * R + 6 * k + j] * sc;
+        }
+        d[13 * R + k] = (float)s[13 * R + k] * sc;
+      }
+    }
+  } else {
+    for (size_t i = 0; i < half.size(); ++i) records[i] = (float)half[i];
+  }
+  return PBA_OK;
+}
+
+int pba_get_records_raw(pba_engine* e, void* dst, size_t bytes) {
+  if (!e || !dst) return fail(PBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (!e->evaluated) return fail(PBA_ERR_NOT_READY, "pba_evaluate first");
+  const size_t n = (size_t)e->n_blocks * e->rec_bytes();
+  if (bytes < n) return fail(PBA_ERR_INVALID_ARGUMENT, "buffer smaller than n_blocks * pba_record_bytes");
+  if (int rc = check_device(e)) return rc;
+  PBA_HIP(hipMemcpyAsync(dst, e->out.p, n, hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
   return PBA_OK;
 }
 
@@ -1291,10 +1454,11 @@ int pba_get_residuals(pba_engine* e, float* residuals, uint8_t* valid) {
     // a residual-only evaluation also wrote its residuals contiguously: one plain device-to-host copy
     if (int rc = enqueue_to_host(e, residuals, mapped_device_ptr(residuals), e->res.p, nb * R * sizeof(float))) return rc;
   } else if (residuals && nb) {
-    // the first R values of every 14R-value record: one pitched device-to-host copy
-    if (e->record_format == PBA_RECORD_F16) {
+    // the first R values of every record (14R values; 15R halves for PBA_RECORD_F16_SCALED, whose residuals are
+    // unscaled): one pitched device-to-host copy
+    if (e->record_format != PBA_RECORD_F32) {
       half.resize(nb * R);
-      PBA_HIP(hipMemcpy2DAsync(half.data(), R * sizeof(_Float16), e->out.p, RF * sizeof(_Float16),
+      PBA_HIP(hipMemcpy2DAsync(half.data(), R * sizeof(_Float16), e->out.p, (size_t)e->rec_bytes(),
                                R * sizeof(_Float16), nb, hipMemcpyDeviceToHost, e->stream));
     } else {
       PBA_HIP(hipMemcpy2DAsync(residuals, R * sizeof(float), e->out.p, RF * sizeof(float), R * sizeof(float), nb,
@@ -1364,6 +1528,23 @@ int pba_device_records(pba_engine* e, float** d_records, uint8_t** d_valid, floa
   if (d_records) *d_records = e->out.p;
   if (d_valid) *d_valid = e->valid.p;
   if (d_costs) *d_costs = e->cost.p;
+  return PBA_OK;
+}
+
+int pba_decode_records_device(pba_engine* e, float* d_out) {
+  if (!e || !d_out) return fail(PBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (!e->evaluated) return fail(PBA_ERR_NOT_READY, "pba_evaluate first");
+  if (int rc = check_device(e)) return rc;
+  if (e->record_format == PBA_RECORD_F32) {
+    PBA_HIP(hipMemcpyAsync(d_out, e->out.p, (size_t)e->n_blocks * e->rec_floats() * sizeof(float),
+                           hipMemcpyDeviceToDevice, e->stream));
+    return PBA_OK;
+  }
+  const int grid = (e->n_blocks + kDecodeBlocks - 1) / kDecodeBlocks;
+  decode_records_kernel<<<grid, kBlockThreads, 0, e->stream>>>(reinterpret_cast<const _Float16*>(e->out.p), d_out,
+                                                               e->n_blocks, e->P,
+                                                               e->record_format == PBA_RECORD_F16_SCALED ? 15 : 14);
+  PBA_HIP(hipGetLastError());
   return PBA_OK;
 }
 

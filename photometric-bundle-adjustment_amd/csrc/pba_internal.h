@@ -901,6 +901,10 @@ struct pba_engine {
   int R() const { return opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC ? P : 2; }
   // values per record: [r | J_host | J_target | J_rho] (14R), + J_intr (8R) with pba_set_optimize_intrinsics
   int rec_floats() const { return (opt_intr ? 22 : 14) * R(); }
+  // device bytes per record as stored: fp32 values, halves, or halves with the scale column (15R, pba.h)
+  int rec_bytes() const {
+    return record_format == PBA_RECORD_F16_SCALED ? 30 * R() : (record_format == PBA_RECORD_F16 ? 2 : 4) * rec_floats();
+  }
 };
 
 namespace pba {

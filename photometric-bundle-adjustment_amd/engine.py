@@ -38,7 +38,7 @@ class OutlierThresholds(C.Structure):
 
 
 OUTLIER_HUGE, OUTLIER_NORMAL, OUTLIER_DISTANCE, OUTLIER_Z = 1, 2, 4, 8
-RECORD_F32, RECORD_F16 = 0, 1
+RECORD_F32, RECORD_F16, RECORD_F16_SCALED = 0, 1, 2
 INTERP_BILINEAR, INTERP_BICUBIC = 0, 1  # pba_set_interpolator
 
 
@@ -196,6 +196,9 @@ def lib(path: Optional[str] = None):
         "pba_outlier_landmarks": ([i32, i32, vp, vp, vp, vp, vp, vp], C.c_int),
         "pba_set_record_format": ([vp, i32], C.c_int),
         "pba_record_format": ([vp], C.c_int),
+        "pba_record_bytes": ([vp], C.c_int),
+        "pba_get_records_raw": ([vp, vp, C.c_size_t], C.c_int),
+        "pba_decode_records_device": ([vp, vp], C.c_int),
         "pba_build_pyramid": ([vp, i32], C.c_int),
         "pba_num_levels": ([vp], C.c_int),
         "pba_set_level": ([vp, i32], C.c_int),
@@ -231,6 +234,23 @@ def _check(rc: int, what: str, L=None):
 
 def _p(a: Optional[np.ndarray]):
     return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def decode_scaled(raw_u16: np.ndarray, P: int) -> np.ndarray:
+    """RECORD_F16_SCALED records (n_blocks, 15·P) as uint16 half bit patterns → (n_blocks, 14·P) float32, in numpy alone.
+
+    Layout per block: [r (P) | J_host (P×6) | J_target (P×6) | J_rho (P) | e (P)]; a Jacobian entry of pixel row k is
+    stored · e[k] (e a power of two, so the product is exact in float32); residuals are unscaled."""
+    raw = np.ascontiguousarray(raw_u16, np.uint16).reshape(-1, 15 * P)
+    h = raw.view(np.float16).astype(np.float32)
+    n = h.shape[0]
+    e = h[:, 14 * P:]
+    out = np.empty((n, 14 * P), np.float32)
+    out[:, :P] = h[:, :P]
+    out[:, P:7 * P] = (h[:, P:7 * P].reshape(n, P, 6) * e[:, :, None]).reshape(n, 6 * P)
+    out[:, 7 * P:13 * P] = (h[:, 7 * P:13 * P].reshape(n, P, 6) * e[:, :, None]).reshape(n, 6 * P)
+    out[:, 13 * P:] = h[:, 13 * P:14 * P] * e
+    return out
 
 
 class Engine:
@@ -336,8 +356,36 @@ class Engine:
         return out
 
     def set_record_format(self, fmt: int):
-        """RECORD_F32 (default) or RECORD_F16 (records stored as IEEE halves; records() still returns floats)."""
+        """RECORD_F32 (default), RECORD_F16 (records stored as IEEE halves, saturating at ±65504) or RECORD_F16_SCALED
+        (halves with one power-of-two scale per pixel row: no clamp); records() returns floats in every format."""
         self._ck(self._L.pba_set_record_format(self._h, fmt), "pba_set_record_format")
+
+    @property
+    def record_format(self) -> int:
+        return self._L.pba_record_format(self._h)
+
+    @property
+    def record_floats(self) -> int:
+        """Values per record as records() returns them (pba_record_floats): 14·R in every record format."""
+        return self._L.pba_record_floats(self._h)
+
+    @property
+    def record_bytes(self) -> int:
+        """Device bytes per record as stored (pba_record_bytes): 4·record, 28·R or 30·R by format."""
+        return self._L.pba_record_bytes(self._h)
+
+    def records_raw(self) -> np.ndarray:
+        """The record array as stored: (n_blocks, record_bytes / itemsize) float32 (RECORD_F32) or uint16 (the halves'
+        bit patterns; decode_scaled() restates the RECORD_F16_SCALED layout)."""
+        dt = np.float32 if self.record_format == RECORD_F32 else np.uint16
+        raw = np.empty((self.n_blocks, self.record_bytes // np.dtype(dt).itemsize), dt)
+        self._ck(self._L.pba_get_records_raw(self._h, _p(raw), raw.nbytes), "pba_get_records_raw")
+        return raw
+
+    def decode_records_device(self, out_ptr: int):
+        """Enqueue the expansion of the records, in any format, to n_blocks·record float32 values at device address
+        out_ptr (pba_decode_records_device)."""
+        self._ck(self._L.pba_decode_records_device(self._h, C.c_void_p(out_ptr)), "pba_decode_records_device")
 
     def records(self):
         rec = np.empty((self.n_blocks, self.record), np.float32)
