@@ -122,7 +122,9 @@ int pba_evaluate_states_device(pba_engine* engine, int32_t n, const double* cons
 int pba_synchronize(pba_engine* engine);
 
 /* Results ---------------------------------------------------------------------------------------- */
-int pba_record_floats(const pba_engine* engine);   /* 14·R (22·R with pba_set_optimize_intrinsics) values per record */
+/* values per record as pba_get_records returns them: 14·R, or — with pba_set_optimize_intrinsics, on geometric and
+ * photometric engines alike — 22·R: [ r(R) | J_host(R×6) | J_target(R×6) | J_rho(R) | J_intr(R×8) ] */
+int pba_record_floats(const pba_engine* engine);
 /* Record storage format (photometric engines): PBA_RECORD_F32 (default) or PBA_RECORD_F16 — IEEE half records,
  * half the HBM write traffic (config C5's "fp16 residuals"; evaluation stays fp64 warp + fp32 chain, rounding
  * only at the store: ≤ 2⁻¹¹ relative per value; values beyond the half range saturate at ±65504 — at full
@@ -148,15 +150,32 @@ int pba_record_floats(const pba_engine* engine);   /* 14·R (22·R with pba_set_
 int pba_set_record_format(pba_engine* engine, int32_t format);
 int pba_record_format(const pba_engine* engine);
 /* device bytes per record as stored: 4·pba_record_floats (PBA_RECORD_F32), 28·R (PBA_RECORD_F16) or 30·R
- * (PBA_RECORD_F16_SCALED).  pba_record_floats stays 14·R: it describes what pba_get_records returns. */
+ * (PBA_RECORD_F16_SCALED).  pba_record_floats stays 14·R in the half formats: it describes what pba_get_records returns.
+ * With pba_set_optimize_intrinsics the records are fp32 only: 88·R bytes. */
 int pba_record_bytes(const pba_engine* engine);
-/* Target-intrinsics Jacobian (geometric engines; BundleAdjustmentOptions::optimize_intrinsics, map_utils.h:339-345):
+/* Target-intrinsics Jacobian (geometric and photometric engines; BundleAdjustmentOptions::optimize_intrinsics,
+ * map_utils.h:339-345):
  * the reference functor takes the TARGET camera's intrinsics as its 4th parameter block (sIntr_c2, reprojection.h:83-86,
  * :108) and unprojects the host pixel with the intrinsics captured at problem build (ref_intrinsics, :93-98; Ceres never
  * writes user memory during a solve without an evaluation callback, so those stay at their initial values).  Enabled,
  * every projection uses the intrinsics state (pba_set_intrinsics_state, 8·n_cams doubles; initially the cameras'),
  * host unprojection keeps the pba_set_cameras values, and each record grows by J_intr (R×8, row-major) after J_rho:
- * 22·R values.  The on-device Gauss-Newton (pba_gn_*, pba_solve) then optimises the intrinsics too: each camera's 8
+ * 22·R values.
+ * Photometric engines: the bearing b_k and a device-sampled I_h,k keep the cameras' values; the domain test, π in
+ * r_k = I_t(π_state(p̃_k)) − I_h,k and the chain ∇I·∂π/∂p̃ of J_host, J_target and J_rho use the state of the TARGET
+ * keyframe's camera; row k of J_intr is [∂I/∂u ∂I/∂v]·∂π/∂k (2×8) at p̃_k (no minus sign, unlike the geometric
+ * r = u_obs − π), with exact zeros in the columns of parameters the model does not use.  An invalid block stores 22·R
+ * zeros, a residual-only evaluation writes r at the 22·R stride.  At pyramid level l the target projects with the
+ * level-l image of the state (fx/2^l, fy/2^l, (c + 0.5)/2^l − 0.5, distortion unchanged) while J_intr stays the
+ * derivative with respect to the level-0 state — the block a caller such as Ceres holds — so its columns 0-3 carry the
+ * factor 2^−l; pba_set_intrinsics_state and pba_get_intrinsics speak of the level-0 state at every level.  The records
+ * are fp32 only: with free intrinsics pba_set_record_format refuses the half formats, and with a half format active
+ * this call refuses (PBA_ERR_INVALID_ARGUMENT either way; J_intr's distortion columns reach ~2.5e4 and a 21-value row
+ * scale is a design of its own).  The on-device Gauss-Newton does not take photometric free intrinsics — its border
+ * kernels are written for 2-row blocks — so every pba_gn_* entry point, pba_solve, pba_solve_pyramid and
+ * pba_solve_distributed(_comm) returns PBA_ERR_INVALID_ARGUMENT instead of solving with the intrinsics held fixed; the
+ * consumer is an outer solver over the records (include/pba_ceres.h, GpuPhotometricIntrinsicsCost).
+ * Geometric engines: the on-device Gauss-Newton (pba_gn_*, pba_solve) then optimises the intrinsics too: each camera's 8
  * intrinsics are 12 unknowns of the reduced camera system after the keyframes' (two 6-dim blocks, the last four pads
  * with identity rows), a dense border of the skyline system (SPARSE_SCHUR keeps the intrinsics blocks among the f-blocks,
  * schur_complement_solver.cc:138-146); k ← k + δk, Ceres' LM diagonal over them too.  The multi-GPU entry points

@@ -21,10 +21,13 @@
 //     bundle_adjustment() keeps its LocalParameterizationSE3 registered unchanged (map_utils.h:331-333).
 //     Alternatively (PoseJacobian::kTangent) the adapter writes [J6 | 0] for SE3TangentParameterization: the SAME
 //     Plus (T·exp(δ), local_parameterization_se3.hpp:43-50) with Jacobian [I₆; 0] — no per-frame P⁺ to form.
-//   * Intrinsics (geometric): given the cameras' intrinsics parameter blocks, the evaluator enables the engine's target-
-//     intrinsics Jacobian (pba_set_optimize_intrinsics) and uploads the blocks' current values before every
+//   * Intrinsics (both residual kinds): given the cameras' intrinsics parameter blocks, the evaluator enables the engine's
+//     target-intrinsics Jacobian (pba_set_optimize_intrinsics) and uploads the blocks' current values before every
 //     evaluation, so Ceres may leave them free (BundleAdjustmentOptions::optimize_intrinsics, map_utils.h:339-345).
-//     Without them, a Jacobian request for an intrinsics block is refused: that Evaluate returns false and Ceres
+//     The target camera then projects with its block's values, the host keeps unprojecting with pba_set_cameras' (the
+//     functor's captured ref_intrinsics, reprojection.h:93-98); the records grow by J_intr (R×8), which
+//     GpuReprojectionCost and GpuPhotometricIntrinsicsCost<P> hand to Ceres as the fourth parameter block's Jacobian.
+//     Without the blocks, a Jacobian request for an intrinsics block is refused: that Evaluate returns false and Ceres
 //     stops with FAILURE instead of optimising with a zero gradient.
 //
 // The loss function stays with Ceres (HuberLoss is applied after Evaluate, residual_block.cc:161-196).
@@ -178,8 +181,8 @@ class GpuEvaluator : public ceres::EvaluationCallback {
  public:
   // poses[f] = T_w_c.data() of keyframe f (7 doubles, user memory Ceres optimises in place);
   // inv_dist[p] = &landmark.inv_depth of point p; intrinsics[c] = calib_cam.intrinsics[c]->data() (8 doubles) when the
-  // geometric problem's intrinsics blocks may be free (optimize_intrinsics), else empty.  The engine must already hold
-  // the problem structure.
+  // problem's intrinsics blocks may be free (optimize_intrinsics; geometric or photometric engine), else empty.  The
+  // engine must already hold the problem structure.
   GpuEvaluator(pba_engine* engine, std::vector<double*> poses, std::vector<double*> inv_dist,
                std::vector<double*> intrinsics = {}, PoseJacobian pose_jacobian = PoseJacobian::kReferenceSE3)
       : engine_(engine), poses_(std::move(poses)), rho_(std::move(inv_dist)), intr_(std::move(intrinsics)),
@@ -201,7 +204,7 @@ class GpuEvaluator : public ceres::EvaluationCallback {
 
   // Called on the solver thread after Ceres has written the evaluation point into the user's parameter memory
   // (program_evaluator.h:157-162).  A Jacobian evaluation reads back the whole records; a residual-only one (the
-  // LM candidate, trust_region_minimizer.cc:761-779) only the residuals, R of every 14R record values.  The
+  // LM candidate, trust_region_minimizer.cc:761-779) only the residuals, R of every 14R (22R) record values.  The
   // evaluation after an accepted step comes with new_evaluation_point = false (trust_region_minimizer.cc:805-822):
   // when the point was already evaluated with Jacobians nothing is recomputed.
   // Where PrepareForEvaluation's time goes (seconds, summed over calls; [0] residual-only, [1] with Jacobians):
@@ -359,7 +362,8 @@ inline void pose_jacobian_7(const GpuEvaluator& ev, int frame, const float* j6, 
 }
 
 // Copy one block's record into Ceres' buffers.  Parameter blocks: T_w_host[7], T_w_target[7], ρ[1], and — for the
-// geometric functor's signature (reprojection.h:83-86) — the target intrinsics[8] (n_intr = 8).
+// geometric functor's signature (reprojection.h:83-86) and the photometric cost with free intrinsics — the target
+// intrinsics[8] (n_intr = 8).
 template <int R>
 inline bool copy_block(const GpuEvaluator& ev, int block, int host, int target, double* residuals, double** jacobians,
                        int n_intr) {
@@ -391,6 +395,24 @@ class GpuPhotometricCost : public ceres::SizedCostFunction<P, 7, 7, 1> {
       : ev_(ev), block_(block), host_(host), target_(target) {}
   bool Evaluate(double const* const* /*parameters*/, double* residuals, double** jacobians) const override {
     return copy_block<P>(*ev_, block_, host_, target_, residuals, jacobians, 0);
+  }
+
+ private:
+  const GpuEvaluator* ev_;
+  int block_, host_, target_;
+};
+
+// Photometric block with the target camera's intrinsics as a fourth parameter block: SizedCostFunction<P, 7, 7, 1, 8>,
+// parameter order (T_w_host, T_w_target, ρ, intr_target) as the reference's reprojection functor orders them
+// (reprojection.h:83-86).  jacobians[3] (P×8 row-major) is the record's tail J_intr = ∇I·∂π/∂k; the evaluator must have
+// been given the intrinsics blocks (else a request for jacobians[3] is refused, as for GpuReprojectionCost).
+template <int P>
+class GpuPhotometricIntrinsicsCost : public ceres::SizedCostFunction<P, 7, 7, 1, 8> {
+ public:
+  GpuPhotometricIntrinsicsCost(const GpuEvaluator* ev, int block, int host, int target)
+      : ev_(ev), block_(block), host_(host), target_(target) {}
+  bool Evaluate(double const* const* /*parameters*/, double* residuals, double** jacobians) const override {
+    return copy_block<P>(*ev_, block_, host_, target_, residuals, jacobians, 8);
   }
 
  private:

@@ -41,17 +41,19 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void make_pair(const double* __restrict__ poses, const int* __restrict__ pair_host,
                                           const int* __restrict__ pair_target, const int* __restrict__ frame_cam,
-                                          const double* __restrict__ cams, PairRec* __restrict__ pairs, int i) {
+                                          const double* __restrict__ cams, const double* __restrict__ cams_t,
+                                          PairRec* __restrict__ pairs, int i) {
   PairRec r;
-  form_pair(poses, frame_cam, cams, pair_host[i], pair_target[i], r);
+  form_pair(poses, frame_cam, cams, cams_t, pair_host[i], pair_target[i], r);
   pairs[i] = r;
 }
 
 __global__ void pair_kernel(const double* __restrict__ poses, const int* __restrict__ pair_host,
                             const int* __restrict__ pair_target, const int* __restrict__ frame_cam,
-                            const double* __restrict__ cams, PairRec* __restrict__ pairs, int n_pairs) {
+                            const double* __restrict__ cams, const double* __restrict__ cams_t,
+                            PairRec* __restrict__ pairs, int n_pairs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_pairs) make_pair(poses, pair_host, pair_target, frame_cam, cams, pairs, i);
+  if (i < n_pairs) make_pair(poses, pair_host, pair_target, frame_cam, cams, cams_t, pairs, i);
 }
 
 // State upload fused with the pair kernel (one launch instead of two copies + pair_kernel): workgroups
@@ -64,7 +66,7 @@ __global__ void state_kernel(const double* __restrict__ src_poses, const double*
                              PairRec* __restrict__ pairs, int n_pairs, int pair_wgs) {
   if ((int)blockIdx.x < pair_wgs) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_pairs) make_pair(src_poses, pair_host, pair_target, frame_cam, cams, pairs, i);
+    if (i < n_pairs) make_pair(src_poses, pair_host, pair_target, frame_cam, cams, cams, pairs, i);
     return;
   }
   const long long stride = (long long)(gridDim.x - pair_wgs) * blockDim.x;
@@ -132,19 +134,44 @@ __device__ __forceinline__ _Float16 rec_val<_Float16>(float v) {
 
 // Storage tag of PBA_RECORD_F16_SCALED: halves with one power-of-two scale per pixel row, 15 halves per row
 // ([r | J_host | J_target | J_rho | e], pba.h).  RecFormat<T>: what a kernel stores (S) and a record's columns per row.
+// Storage tag of the fp32 records with free target intrinsics (pba_set_optimize_intrinsics): 22 floats per row,
+// [r | J_host | J_target | J_rho | J_intr (P×8)].
 struct ScaledF16 {};
+struct IntrF32 {};
 template <class T>
 struct RecFormat {
   using S = T;
   static constexpr int kCols = 14;
   static constexpr bool kScaled = false;
+  static constexpr bool kIntr = false;
 };
 template <>
 struct RecFormat<ScaledF16> {
   using S = _Float16;
   static constexpr int kCols = 15;
   static constexpr bool kScaled = true;
+  static constexpr bool kIntr = false;
 };
+template <>
+struct RecFormat<IntrF32> {
+  using S = float;
+  static constexpr int kCols = 22;
+  static constexpr bool kScaled = false;
+  static constexpr bool kIntr = true;
+};
+
+// Row px of J_intr (8 floats at 14·P + 8·px of the block's staged record): two 16-B LDS writes when the row is 16-B
+// aligned — a block's record is 88·P bytes and the row starts 56·P + 32·px into it, so for even P — else four 8-B ones.
+__device__ __forceinline__ void stage_intr(float* s_rec, int P, int px, const float (&ji)[8]) {
+  float* d = s_rec + 14 * P + 8 * px;
+  if ((P & 1) == 0) {
+    reinterpret_cast<f32x4*>(d)[0] = f32x4{ji[0], ji[1], ji[2], ji[3]};
+    reinterpret_cast<f32x4*>(d)[1] = f32x4{ji[4], ji[5], ji[6], ji[7]};
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) reinterpret_cast<float2*>(d)[q] = make_float2(ji[2 * q], ji[2 * q + 1]);
+  }
+}
 
 // Store a workgroup's contiguous record slab (LDS → global): 16-B non-temporal stores when the slab is 16-B
 // aligned, 4-B or 2-B stores otherwise (odd patterns in fp16).
@@ -238,7 +265,8 @@ __device__ __forceinline__ void stage_row_scaled(_Float16* s_rec, int lb, int P,
   }
 }
 
-template <int PM, int LPB, int MODE, class T>  // PM = camera model + 4 · interpolator; T = float, _Float16 or ScaledF16
+// PM = camera model + 4 · interpolator; T = float, _Float16, ScaledF16 or IntrF32 (RecFormat)
+template <int PM, int LPB, int MODE, class T>
 __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const KernelArgs a) {
   constexpr int BPW = kBlockThreads / LPB;  // blocks per workgroup
   constexpr bool JAC = MODE == 1;
@@ -270,7 +298,10 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
   }
   const float Ih = act ? a.host_int[(long long)pt * P + k] : 0.0f;
   __syncthreads();
-  const Row row = photometric_row<PM, JAC>(a, s_tb[lb], off, Ih);  // dead lanes evaluate a staged block, masked by act
+  constexpr bool INTR = JAC && RecFormat<T>::kIntr;
+  float ji[8];
+  // dead lanes evaluate a staged block, masked by act
+  const Row row = photometric_row<PM, JAC, TileBlock, false, INTR>(a, s_tb[lb], off, Ih, nullptr, ji);
   // per-block validity (ballot over the wave: the block's LPB lanes are an aligned bit field) and ‖r‖²
   const int ok = group_all<LPB>(act ? row.ok : 1);
   const float s = group_sum<LPB>(act ? row.r * row.r : 0.0f);
@@ -318,6 +349,13 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
       s_rec[k] = (S)0.0f;
       for (int j = 0; j < 6; ++j) h[j] = t[j] = (S)0.0f;
       s_rec[13 * P + k] = (S)0.0f;
+    }
+    if constexpr (INTR) {
+      if (!ok) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ji[j] = 0.0f;
+      }
+      stage_intr(s_rec, P, k, ji);
     }
   }
   __syncthreads();
@@ -393,8 +431,10 @@ constexpr int kMultiThreads = 32 * RecFormat<T>::kCols * 8 * PPL * (int)sizeof(t
 // kMultiWaves: the waves per SIMD the camera-table form is compiled for.  6, except the scaled-half records of 9–16 and
 // 25–32 px: held to 80 VGPRs those spilled 8–28 B per lane, and six workgroups are out of reach of the 25–32-px stage
 // anyway (15 halves per row: 30.7 KB of stage per workgroup, 4 per CU).
+// The 22-column records (IntrF32; the camera-table form serves their 9–16 px): 45 KB of stage per workgroup at 16 px,
+// 3 workgroups per CU, so 3 waves per SIMD is all the LDS allows and the rows keep their registers.
 template <int PPL, class T>
-constexpr int kMultiWaves = RecFormat<T>::kScaled && PPL != 3 ? 5 : 6;
+constexpr int kMultiWaves = RecFormat<T>::kIntr ? 3 : (RecFormat<T>::kScaled && PPL != 3 ? 5 : 6);
 
 template <int PM, int MODE, class T, int PPL, bool CT = false, bool C1 = false>
 __global__ __launch_bounds__((kMultiThreads<PPL, T>))
@@ -447,11 +487,16 @@ void photometric_block_kernel_multi(const KernelArgs a) {
   auto pixel = [&](int j, float ih) {
     const int px = k + LPB * j;
     const bool act = live && px < P;
-    const Row row = photometric_row<PM, JAC, TB, C1>(a, s_tb[lb], s_pat[px < P ? px : 0], ih, s_cam);  // masked by act
+    constexpr bool INTR = JAC && RecFormat<T>::kIntr;
+    float ji[8];
+    const Row row = photometric_row<PM, JAC, TB, C1, INTR>(a, s_tb[lb], s_pat[px < P ? px : 0], ih, s_cam, ji);  // masked by act
     okl &= act ? row.ok : 1;
     s += act ? row.r * row.r : 0.0f;
     if constexpr (JAC && RecFormat<T>::kScaled) stage_row_scaled(s_rec, lb, P, px, row, act);
     else if constexpr (JAC) stage_row<S>(s_rec, P, px, row, act);
+    if constexpr (INTR) {
+      if (act) stage_intr(s_rec, P, px, ji);
+    }
     return row.r;
   };
   if constexpr (JAC) {
@@ -506,6 +551,10 @@ void photometric_block_kernel_multi(const KernelArgs a) {
       s_rec[13 * P + px] = (S)0.0f;
       for (int q = 0; q < 6; ++q) s_rec[P + 6 * px + q] = s_rec[7 * P + 6 * px + q] = (S)0.0f;
       if constexpr (kCols == 15) s_rec[14 * P + px] = (S)0.0f;
+      if constexpr (RecFormat<T>::kIntr) {
+        const float z[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        stage_intr(s_rec, P, px, z);
+      }
     }
   }
   __syncthreads();
@@ -659,11 +708,14 @@ void launch_geometric(pba_engine* e, const KernelArgs& ka, int mode) {
 template <int PM>
 void launch_photometric(pba_engine* e, KernelArgs ka, int mode) {
   const bool h = e->record_format == PBA_RECORD_F16, hs = e->record_format == PBA_RECORD_F16_SCALED;
+  const bool in = e->opt_intr;  // 22-column fp32 records (the half formats are refused with free intrinsics)
   if (e->P <= 8) {
     const int grid = (int)(((long long)e->n_blocks * 8 + kBlockThreads - 1) / kBlockThreads);
     e->last_grid = grid;
     ka.slab_wt = grid <= kSlabWtGrid;  // one wave of workgroups: write-through record stores (store_slab)
-    if (mode == 1 && hs) photometric_block_kernel<PM, 8, 1, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    if (mode == 1 && in) photometric_block_kernel<PM, 8, 1, IntrF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    else if (mode == 0 && in) photometric_block_kernel<PM, 8, 0, IntrF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    else if (mode == 1 && hs) photometric_block_kernel<PM, 8, 1, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 0 && hs) photometric_block_kernel<PM, 8, 0, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 1 && h) photometric_block_kernel<PM, 8, 1, _Float16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 1) photometric_block_kernel<PM, 8, 1, float><<<grid, kBlockThreads, 0, e->stream>>>(ka);
@@ -694,7 +746,9 @@ void launch_photometric(pba_engine* e, KernelArgs ka, int mode) {
     }                                                                                                   \
   }
 #define PBA_LAUNCH_PPL(PPL)                                        \
-  if (mode == 1 && hs) PBA_LAUNCH_ONE(PPL, 1, ScaledF16)           \
+  if (mode == 1 && in) PBA_LAUNCH_ONE(PPL, 1, IntrF32)             \
+  else if (mode == 0 && in) PBA_LAUNCH_ONE(PPL, 0, IntrF32)        \
+  else if (mode == 1 && hs) PBA_LAUNCH_ONE(PPL, 1, ScaledF16)      \
   else if (mode == 0 && hs) PBA_LAUNCH_ONE(PPL, 0, ScaledF16)      \
   else if (mode == 1 && h) PBA_LAUNCH_ONE(PPL, 1, _Float16)        \
   else if (mode == 1) PBA_LAUNCH_ONE(PPL, 1, float)                \
@@ -749,6 +803,7 @@ KernelArgs make_kernel_args(pba_engine* e, const PairRec* pairs, const double* r
   ka.intr_d = e->intr_d.p;
   ka.intr_t = e->opt_intr ? e->intr_state.p : e->intr.p;
   ka.intr_t_d = e->opt_intr ? e->intr_state_d.p : e->intr_d.p;
+  ka.intr_scale = std::ldexp(1.0f, -e->level);
   ka.block_point = e->block_point.p;
   ka.block_pair = e->block_pair.p;
   ka.block_pp = e->block_pp.p;
@@ -772,8 +827,12 @@ KernelArgs make_kernel_args(pba_engine* e, const PairRec* pairs, const double* r
 }
 
 void launch_pairs(pba_engine* e, const double* poses, PairRec* pairs) {
-  pair_kernel<<<(e->n_pairs + 255) / 256, 256, 0, e->stream>>>(poses, e->pair_host.p, e->pair_target.p,
-                                                               e->frame_cam.p, e->intr_d.p, pairs, e->n_pairs);
+  // a photometric pair's target part is the intrinsics state's (the geometric kernels read the state themselves and
+  // keep the cameras in the table, as the Gauss-Newton kernels expect)
+  const bool state = e->opt_intr && e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC;
+  pair_kernel<<<(e->n_pairs + 255) / 256, 256, 0, e->stream>>>(poses, e->pair_host.p, e->pair_target.p, e->frame_cam.p,
+                                                               e->intr_d.p, state ? e->intr_state_d.p : e->intr_d.p,
+                                                               pairs, e->n_pairs);
 }
 
 int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, double* wg_red, int* n_slots,
@@ -794,7 +853,7 @@ int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, dou
 
 extern "C" {
 
-int pba_version(void) { return 100; }
+int pba_version(void) { return 101; }
 
 const char* pba_status_string(int s) {
   switch (s) {
@@ -890,26 +949,53 @@ int pba_set_cameras(pba_engine* e, int32_t n_cams, const double* intrinsics) {
   reset_pyramid(e);
   if (int rc = upload_cameras(e, n_cams, intrinsics, e->intr, e->intr_d)) return rc;
   e->n_cams = n_cams;
-  if (e->opt_intr) return upload_cameras(e, n_cams, intrinsics, e->intr_state, e->intr_state_d);
+  e->cams_h.assign(intrinsics, intrinsics + 8 * (size_t)n_cams);
+  if (e->opt_intr) {
+    e->intr_state_h = e->cams_h;
+    return upload_intrinsics_state(e);
+  }
   return PBA_OK;
 }
 
+}  // extern "C"
+
+namespace pba {
+namespace detail {
+
+// intr_state / intr_state_d from the level-0 state intr_state_h: at pyramid level l the target projects with the
+// level-l image of the state, fx/2^l, fy/2^l, c_l = (c + 0.5)/2^l − 0.5, distortion unchanged (pba_pyramid.hip).
+int upload_intrinsics_state(pba_engine* e) {
+  if (int rc = check_device(e)) return rc;  // (reset_pyramid reaches this from calls that touch no device otherwise)
+  std::vector<double> k = e->intr_state_h;
+  const double s = std::ldexp(1.0, -e->level);
+  if (e->level > 0)
+    for (int c = 0; c < e->n_cams; ++c) {
+      double* r = k.data() + 8 * (size_t)c;
+      r[0] *= s; r[1] *= s; r[2] = (r[2] + 0.5) * s - 0.5; r[3] = (r[3] + 0.5) * s - 0.5;
+    }
+  return upload_cameras(e, e->n_cams, k.data(), e->intr_state, e->intr_state_d);
+}
+
+}  // namespace detail
+}  // namespace pba
+
+extern "C" {
+
 int pba_set_optimize_intrinsics(pba_engine* e, int32_t enable) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
-  if (enable && e->opt.residual_kind != PBA_RESIDUAL_GEOMETRIC)
-    return fail(PBA_ERR_INVALID_ARGUMENT, "intrinsics optimisation is geometric only");
+  if (enable && e->record_format != PBA_RECORD_F32)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics need PBA_RECORD_F32 records (J_intr has no half format)");
   if (enable && e->n_cams <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_cameras first");
   if (int rc = check_device(e)) return rc;
   const bool on = enable != 0;
-  if (on && !e->opt_intr) {  // the state starts at the cameras' intrinsics
-    std::vector<double> k((size_t)kCamD * e->n_cams), k8(8 * (size_t)e->n_cams);
-    PBA_HIP(hipMemcpy(k.data(), e->intr_d.p, sizeof(double) * k.size(), hipMemcpyDeviceToHost));
-    for (int c = 0; c < e->n_cams; ++c)
-      for (int j = 0; j < 8; ++j) k8[8 * c + j] = k[(size_t)kCamD * c + j];
-    if (int rc = upload_cameras(e, e->n_cams, k8.data(), e->intr_state, e->intr_state_d)) return rc;
+  if (on && !e->opt_intr) {  // the state starts at the cameras' (level-0) intrinsics
+    e->intr_state_h = e->cams_h;
+    if (int rc = upload_intrinsics_state(e)) return rc;
   }
   e->opt_intr = on;
   e->evaluated = false;
+  e->res_fresh = false;
+  e->pairs_fresh = false;  // (a photometric pair's target part is the state's)
   e->gn.prepared = false;  // the reduced camera system gains / loses its intrinsics border
   if (e->n_blocks > 0) PBA_HIP(e->out.resize((size_t)e->n_blocks * e->rec_floats()));
   return PBA_OK;
@@ -918,6 +1004,10 @@ int pba_set_optimize_intrinsics(pba_engine* e, int32_t enable) {
 int pba_get_intrinsics(pba_engine* e, double* intrinsics) {
   if (!e || !intrinsics) return fail(PBA_ERR_INVALID_ARGUMENT, "null argument");
   if (e->n_cams <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_cameras first");
+  if (e->opt_intr && e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC) {  // the level-0 state, whatever level is active
+    std::copy(e->intr_state_h.begin(), e->intr_state_h.end(), intrinsics);
+    return PBA_OK;
+  }
   if (int rc = check_device(e)) return rc;
   std::vector<double> k((size_t)kCamD * e->n_cams);
   PBA_HIP(hipMemcpyAsync(k.data(), e->opt_intr ? e->intr_state_d.p : e->intr_d.p, sizeof(double) * k.size(),
@@ -932,7 +1022,12 @@ int pba_set_intrinsics_state(pba_engine* e, const double* intrinsics) {
   if (!e || !intrinsics) return fail(PBA_ERR_INVALID_ARGUMENT, "null argument");
   if (!e->opt_intr) return fail(PBA_ERR_NOT_READY, "pba_set_optimize_intrinsics first");
   if (int rc = check_device(e)) return rc;
-  return upload_cameras(e, e->n_cams, intrinsics, e->intr_state, e->intr_state_d);
+  for (int c = 0; c < e->n_cams; ++c)
+    if (!((float)intrinsics[8 * c] != 0.0f && (float)intrinsics[8 * c + 1] != 0.0f))
+      return fail(PBA_ERR_INVALID_ARGUMENT, "zero focal length");
+  e->intr_state_h.assign(intrinsics, intrinsics + 8 * (size_t)e->n_cams);
+  e->pairs_fresh = e->pairs_fresh && e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC;
+  return upload_intrinsics_state(e);
 }
 
 // Per-block {point, host, target, host_cam << 16 | target_cam} for the fused-state prologue (pba_internal.h
@@ -1288,6 +1383,8 @@ int pba_set_record_format(pba_engine* e, int32_t format) {
     return fail(PBA_ERR_INVALID_ARGUMENT, "unknown record format");
   if (format != PBA_RECORD_F32 && e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC)
     return fail(PBA_ERR_INVALID_ARGUMENT, "fp16 records are photometric only");
+  if (format != PBA_RECORD_F32 && e->opt_intr)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics need PBA_RECORD_F32 records (J_intr has no half format)");
   e->record_format = format;
   e->evaluated = false;
   e->res_fresh = false;

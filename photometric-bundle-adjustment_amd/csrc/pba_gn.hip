@@ -2825,6 +2825,10 @@ int ensure_prepared(pba_engine* e) {
   if (!e->state_set) return fail(PBA_ERR_NOT_READY, "pba_set_state first");
   if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC && (!e->have_images || e->P <= 0))
     return fail(PBA_ERR_NOT_READY, "images/pattern missing");
+  // the border kernels take 2-row (geometric) blocks: without this the solve would hold the intrinsics fixed (nc = 0)
+  if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC && e->opt_intr)
+    return fail(PBA_ERR_INVALID_ARGUMENT,
+                "the on-device Gauss-Newton solve does not support free intrinsics on a photometric engine");
   if (int rc = check_device(e)) return rc;
   if (!e->gn.prepared)
     if (int rc = gn_prepare(e)) return rc;

@@ -111,14 +111,15 @@ __device__ __forceinline__ void camera_kf_part(const uint4& part, int q, float* 
                                         (float)__hiloint2double((int)part.w, (int)part.z));
   reinterpret_cast<float2*>(kf)[q] = v;
 }
-__device__ __forceinline__ void pair_cameras(const double* __restrict__ cams, int h, int t, int hc, int tc,
-                                             PairRec& r) {
+// cams: the cameras (host unprojection); cams_t: the target projection's records — the cameras, or the intrinsics state
+__device__ __forceinline__ void pair_cameras(const double* __restrict__ cams, const double* __restrict__ cams_t, int h,
+                                             int t, int hc, int tc, PairRec& r) {
   r.host_cam = hc;
   r.target_cam = tc;
   r.target = t;
   r.host = h;
   const double* hk = cams + kCamD * hc + kCamHk;
-  const double* tk = cams + kCamD * tc;
+  const double* tk = cams_t + kCamD * tc;
 #pragma unroll
   for (int j = 0; j < kCamK; ++j) {
     r.hk[j] = hk[j];
@@ -127,10 +128,11 @@ __device__ __forceinline__ void pair_cameras(const double* __restrict__ cams, in
   camera_kf(tk, r.kf);
 }
 __device__ __forceinline__ void form_pair(const double* __restrict__ poses, const int* __restrict__ frame_cam,
-                                          const double* __restrict__ cams, int h, int t, PairRec& r) {
+                                          const double* __restrict__ cams, const double* __restrict__ cams_t, int h,
+                                          int t, PairRec& r) {
   pair_rotation(poses + 7 * h, poses + 7 * t, r);
   pair_translation(poses + 7 * h, poses + 7 * t, r);
-  pair_cameras(cams, h, t, frame_cam[h], frame_cam[t], r);
+  pair_cameras(cams, cams_t, h, t, frame_cam[h], frame_cam[t], r);
 }
 
 // One block of a workgroup's tile, staged in LDS by stage_tile(): its pair record and its point.
@@ -190,8 +192,9 @@ struct KernelArgs {
   double umax, vmax;             // interpolation clamp bounds W + 1, H + 1
   const float* intr;             // 8 floats per camera (Jacobian chain)
   const double* intr_d;          // kCamD doubles per camera (warp / projection; pba_device.h)
-  const float* intr_t;           // the target cameras' projection constants (geometric kernels): intr, or the
-  const double* intr_t_d;        // intrinsics state of pba_set_optimize_intrinsics (host unprojection stays on intr_d)
+  const float* intr_t;           // the target cameras' projection constants: intr, or the intrinsics state of
+  const double* intr_t_d;        // pba_set_optimize_intrinsics at the active level (host unprojection stays on intr_d)
+  float intr_scale;              // 2^−level: ∂(level-l fx, fy, cx, cy)/∂(level-0 state), J_intr columns 0-3 (photometric)
   const int* block_point;
   const int* block_pair;
   const int2* block_pp;          // per block {point, pair}
@@ -224,8 +227,8 @@ struct KernelArgs {
 __device__ __forceinline__ CamView single_camera(const KernelArgs& a) {
   typedef const __attribute__((address_space(4))) double cdouble;
   typedef const __attribute__((address_space(4))) float cfloat;
-  return {(const double*)(cdouble*)(a.intr_d + kCamHk), (const double*)(cdouble*)a.intr_d,
-          (const float*)(cfloat*)a.intr};
+  return {(const double*)(cdouble*)(a.intr_d + kCamHk), (const double*)(cdouble*)a.intr_t_d,
+          (const float*)(cfloat*)a.intr_t};
 }
 
 // XCD-aware tile order: consecutive logical tiles (→ neighbouring host keyframes → shared target images)
@@ -334,7 +337,8 @@ __device__ __forceinline__ int stage_tile(const KernelArgs& a, TileBlock* s_tb, 
       t[j] = T[j];
     }
     const int hc = br.w >> 16, tc = br.w & 0xffff, kc = k & 7;
-    const uint4 cam = reinterpret_cast<const uint4*>(a.intr_d + (kc < 4 ? kCamD * hc + kCamHk : kCamD * tc))[kc & 3];
+    // (the host part from the cameras, the target part from the intrinsics state: intr_t_d = intr_d unless it is free)
+    const uint4 cam = reinterpret_cast<const uint4*>(kc < 4 ? a.intr_d + kCamD * hc + kCamHk : a.intr_t_d + kCamD * tc)[kc & 3];
     const uint4 ur = reinterpret_cast<const uint4*>(a.u_ref)[br.x];
     const double rho = a.rho[br.x];
     // every load above completes here, before the lanes diverge (otherwise the compiler sinks each load into the
@@ -438,7 +442,7 @@ __device__ __forceinline__ void stage_tile_wg(const KernelArgs& a, TileBlock* s_
     }
   } else if (w == 2) {
     const bool tgt = lane >= 32;
-    const uint4* src = reinterpret_cast<const uint4*>(a.intr_d + (tgt ? kCamD * (br.w & 0xffff) : kCamD * (br.w >> 16) + kCamHk));
+    const uint4* src = reinterpret_cast<const uint4*>(tgt ? a.intr_t_d + kCamD * (br.w & 0xffff) : a.intr_d + kCamD * (br.w >> 16) + kCamHk);
     uint4 c[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) c[q] = src[q];
@@ -500,7 +504,7 @@ __device__ __forceinline__ void stage_tile_wg_ct(const KernelArgs& a, TileBlockC
     // lane = camera c (lane >> 3) × part q (lane & 7): q < 4 → hk part q, q ≥ 4 → tk part q − 4 (+ its fp32 kf)
     const int c = lane >> 3, q = lane & 7;
     if (c < n_cams) {
-      const uint4 v = reinterpret_cast<const uint4*>(a.intr_d + (q < 4 ? kCamD * c + kCamHk : kCamD * c))[q & 3];
+      const uint4 v = reinterpret_cast<const uint4*>(q < 4 ? a.intr_d + kCamD * c + kCamHk : a.intr_t_d + kCamD * c)[q & 3];
       uint4* d = reinterpret_cast<uint4*>(s_cam + c);
       d[q] = v;  // hk parts 0-3, tk parts 4-7 (CamRec: hk then tk, contiguous)
       if (q >= 4) camera_kf_part(v, q - 4, s_cam[c].kf);
@@ -543,9 +547,12 @@ __device__ __forceinline__ void adopt_state(const KernelArgs& a) {
 // Ih = host intensity I_h,k.
 // PM = camera model + 4 · interpolator (pba_device.h cam_of / interp_of).
 // TB = TileBlock (cameras in the block), or TileBlockC with the LDS camera table `tab`.
-template <int PM, bool JAC, class TB = TileBlock, bool C1 = false>
+// INTR (with JAC): also ji[0..7] = ∇I · ∂π/∂k at p̃, the row of J_intr with respect to the level-0 intrinsics state of
+// the target's camera (no minus sign: r = I_t(π) − I_h).  fp32 (project_intr_jac) on the fp64 projection's 1/den;
+// KB4's θ is the fp64 projection's (pba_device.h).  Columns of parameters the model does not use are exact zeros.
+template <int PM, bool JAC, class TB = TileBlock, bool C1 = false, bool INTR = false>
 __device__ __forceinline__ Row photometric_row(const KernelArgs& a, const TB& tb, float2 off, float Ih,
-                                               const CamRec* tab = nullptr) {
+                                               const CamRec* tab = nullptr, float* ji = nullptr) {
   constexpr int MODEL = cam_of(PM);
   Row o;
   const auto& pp = pose_of(tb);
@@ -589,6 +596,15 @@ __device__ __forceinline__ Row photometric_row(const KernelArgs& a, const TB& tb
       project_jac<MODEL>(cv.tk, p, iden, dud, dvd);
       const Vec3d td = {pp.t[0], pp.t[1], pp.t[2]};
       o.jr = (float)((double)gx * dot(dud, td) + (double)gy * dot(dvd, td));
+    }
+    if (INTR) {
+      float ku[8], kv[8];
+      if (MODEL == CAM_KB4)  // the same expression as project()'s θ: one fp64 atan2 for both
+        project_intr_jac_kb4(cv.kf, pf, (float)iden, (float)atan2(sqrt(p.x * p.x + p.y * p.y), p.z), ku, kv);
+      else
+        project_intr_jac<MODEL>(cv.kf, pf, (float)iden, ku, kv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ji[j] = (gx * ku[j] + gy * kv[j]) * (j < 4 ? a.intr_scale : 1.0f);
     }
   }
   return o;
@@ -880,8 +896,12 @@ struct pba_engine {
   int interp = PBA_INTERP_BILINEAR;  // pba_set_interpolator
   bool host_int_sampled = false;     // I_h,k sampled on the device (pba_set_points without intensities)
   bool opt_intr = false;             // pba_set_optimize_intrinsics: target intrinsics state + J_intr record tail
-  pba::detail::DevBuf<float> intr_state;     // its projection constants (8 floats per camera)
+  pba::detail::DevBuf<float> intr_state;     // its projection constants (8 floats per camera) at the active level
   pba::detail::DevBuf<double> intr_state_d;  // and fp64 camera records (kCamD per camera)
+  // photometric engines: the level-0 state as the caller set it (8 per camera); the device copy above is its image at
+  // the active pyramid level (upload_intrinsics_state: pba_set_intrinsics_state, pba_set_level)
+  std::vector<double> intr_state_h;
+  std::vector<double> cams_h;        // pba_set_cameras' intrinsics (8 per camera, level 0): where the state starts
   bool state_set = false;
   bool pairs_fresh = false;          // pairs hold T_th of the current poses (pba_set_state_device forms them)
   bool evaluated = false;
@@ -933,6 +953,9 @@ int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, dou
 int comm_allreduce(pba_comm* c, double* buf, long long count, hipStream_t stream);
 int comm_rank(const pba_comm* c);
 int comm_size(const pba_comm* c);
+
+// The intrinsics state's device copy at the active pyramid level from intr_state_h (pba_engine.hip; photometric engines).
+int upload_intrinsics_state(pba_engine* e);
 
 // Pyramid (pba_pyramid.hip): back to level 0 and drop the levels; I_h,k sampled from the active level's host images.
 void reset_pyramid(pba_engine* e);

@@ -99,8 +99,10 @@ namespace detail {
 
 // Back to level 0 and drop the pyramid (any set_* call that changes images, cameras, pattern or points).
 void reset_pyramid(pba_engine* e) {
+  const bool restate = e->level > 0 && e->opt_intr && e->n_cams > 0;
   if (e->level > 0 && e->level < (int)e->pyr.size()) swap_level(e, *e->pyr[e->level]);
   e->level = 0;
+  if (restate) (void)upload_intrinsics_state(e);
   e->pyr.clear();
   e->pairs_fresh = false;
 }
@@ -246,6 +248,7 @@ int pba_set_level(pba_engine* e, int32_t level) {
   e->level = level;
   e->pairs_fresh = false;
   e->evaluated = false;
+  if (e->opt_intr) return upload_intrinsics_state(e);  // the intrinsics state's image at this level
   return PBA_OK;
 }
 

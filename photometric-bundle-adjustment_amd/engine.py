@@ -366,12 +366,14 @@ class Engine:
 
     @property
     def record_floats(self) -> int:
-        """Values per record as records() returns them (pba_record_floats): 14·R in every record format."""
+        """Values per record as records() returns them (pba_record_floats): 14·R in every record format, 22·R with
+        set_optimize_intrinsics (fp32 records only)."""
         return self._L.pba_record_floats(self._h)
 
     @property
     def record_bytes(self) -> int:
-        """Device bytes per record as stored (pba_record_bytes): 4·record, 28·R or 30·R by format."""
+        """Device bytes per record as stored (pba_record_bytes): 4·record_floats (56·R, or 88·R with free intrinsics),
+        28·R or 30·R by format."""
         return self._L.pba_record_bytes(self._h)
 
     def records_raw(self) -> np.ndarray:
@@ -565,13 +567,19 @@ class Engine:
                "pba_solve_distributed_comm")
         return s.as_dict()
 
-    # -- target intrinsics (geometric, optimize_intrinsics) -----------------------------------------
+    # -- target intrinsics (optimize_intrinsics; geometric and photometric engines) ---------------------
     def set_optimize_intrinsics(self, enable: bool = True):
+        """Free target intrinsics: the target camera projects with the intrinsics state (set_intrinsics_state; it starts
+        at the cameras' values), the host keeps the cameras', and the records grow to 22·R values with J_intr (R×8) as
+        their tail (split_record).  Photometric engines: fp32 records only, and the on-device solve refuses."""
         self._ck(self._L.pba_set_optimize_intrinsics(self._h, int(bool(enable))), "pba_set_optimize_intrinsics")
         self.record = self._L.pba_record_floats(self._h)
 
     def set_intrinsics_state(self, intrinsics: np.ndarray):
+        """(n_cams, 8) level-0 intrinsics; at a pyramid level the engine projects with their image at that level."""
         k = np.ascontiguousarray(intrinsics, np.float64)
+        if k.size != 8 * self._n_cams:
+            raise ValueError("intrinsics state shape mismatch")
         self._ck(self._L.pba_set_intrinsics_state(self._h, _p(k)), "pba_set_intrinsics_state")
 
     def get_state(self):
@@ -722,5 +730,10 @@ def outlier_landmarks(n_points: int, obs_point, obs_frame, flags, obs_is_outlier
 
 
 def split_record(rec: np.ndarray, R: int):
+    """(r, J_host, J_target, J_rho) views of a record array — and J_intr (n, R, 8) as a fifth when the records carry it
+    (22·R values per record: set_optimize_intrinsics)."""
     n = rec.shape[0]
-    return rec[:, :R], rec[:, R:7 * R].reshape(n, R, 6), rec[:, 7 * R:13 * R].reshape(n, R, 6), rec[:, 13 * R:14 * R]
+    parts = (rec[:, :R], rec[:, R:7 * R].reshape(n, R, 6), rec[:, 7 * R:13 * R].reshape(n, R, 6), rec[:, 13 * R:14 * R])
+    if rec.shape[1] == 22 * R:
+        parts += (rec[:, 14 * R:22 * R].reshape(n, R, 8),)
+    return parts
