@@ -1,8 +1,11 @@
-// pba_gn.h — what the Gauss-Newton units share: pba_gn.hip (elimination, assembly, update, LM loops),
-// pba_gn_linearize.hip (the linearisation) and pba_gn_solve_cr.hip (v4f64; the solvers' own interface is pba_gn_solve.h).
+// pba_gn.h — what the Gauss-Newton device units share: pba_gn.hip (elimination, assembly, update, LM loops),
+// pba_gn_linearize.hip (the linearisation), pba_gn_intr.hip (free intrinsics; its own interface is pba_gn_intr.h) and
+// pba_gn_solve_cr.hip (v4f64; the solvers' own interface is pba_gn_solve.h).  The layout constants that the host-only
+// symbolic analysis (pba_gn_plan.cpp) shares with them come from pba_gn_plan.h.
 // The pipeline of a trial is described in pba_gn.hip.
 #pragma once
 
+#include "pba_gn_plan.h"
 #include "pba_internal.h"
 
 namespace pba {
@@ -11,12 +14,7 @@ namespace detail {
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 constexpr int kPd = 8;            // point data per GN block: [H_ρρ, g_ρ, W_t(6)] (blk_schur)
-constexpr int SLOT_LIN_BASE = 42;  // H_hh(36) + g_h(6)
-constexpr int SLOT_LIN_T = 78;     // H_ht(36) + H_tt(36) + g_t(6)
-
-// At most this many targets per linearise chunk (gn_prepare cuts chunks there): a wave's blocks then hold ≤ 4 target
-// runs, so its per-run product sets (fp64) fit the LDS the fp32 ones took for 8.
-constexpr int kChunkTargets = 4;
+// (SLOT_LIN_*, kChunkTargets, SCHUR_PTS, SCHUR_W, C_*: pba_gn_plan.h, shared with the host-only plan unit)
 
 // LM decision record kept on the device by the single-GPU loop (lm_decide_kernel).
 // The trial's outcome, then the trust-region state the next trial runs with (λ = 1/radius, read by the kernels), the
@@ -40,6 +38,11 @@ struct LmView {
 __device__ __forceinline__ LmView lm_view(const double* lm) {
   return LmView{lm[kLmDone], lm[kLmSet], lm[kLmLambda], lm[kLmAccept]};
 }
+// λ of a kernel: the record's, or — NaN there, host-driven steps — the kernel's argument
+__device__ __forceinline__ double lm_lambda(const LmView& v, double lambda) { return isnan(v.lambda) ? lambda : v.lambda; }
+
+// Multi-GPU exchange: the tail of a row after its blocks (export_band_kernel, and the border rows of pba_gn_intr.hip)
+constexpr int EX_TAIL = 24;  // g(6) | g_direct(6) | diag(A)(6) | observed | pad
 
 struct LinArgs {
   const int4* lin_rec;      // chunk slot → {block, point, pair | local target slot << 24, GN position (blk_schur index)}

@@ -24,8 +24,11 @@
 //                          14-column form (geometric rows, PBA_LIN_LEGACY).  Both in pba_gn_linearize.hip.
 //   schur_free_decide_kernel  the λ-free point elimination of the new linearisation (P/(1 + λ) in the assembly) and,
 //                          in 16 workgroups counted in by an atomic, the fixed-order trial sums and Ceres' decision.
-// Free intrinsics add intr_rows_kernel and the border kernels (intr_border_*) after the elimination; several GPUs
-// exchange the per-rank systems (export_band_kernel, import_kernel / import_sky_kernel, dist_* kernels).
+// Free intrinsics add intr_rows_kernel and the border kernels (intr_border_*) after the elimination: pba_gn_intr.hip,
+// called through pba_gn_intr.h (only AcceptCopy and intr_update_frame, fused into kernels of this unit, are here);
+// several GPUs exchange the per-rank systems (export_band_kernel, import_kernel / import_sky_kernel, dist_* kernels).
+// The index structures all of these read — GN order, chunks, slot offsets, skyline profile, contribution and border
+// lists — come from the host-only symbolic analysis build_gn_plan (pba_gn_plan.cpp); gn_prepare uploads them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,28 +39,19 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <map>
-#include <numeric>
 #include <string>
 #include <thread>
 #include <utility>
 #include <vector>
 
 #include "pba_gn.h"
+#include "pba_gn_intr.h"
 #include "pba_gn_solve.h"
 
 using namespace pba;
 using namespace pba::detail;
 
 namespace {
-
-#ifndef PBA_SCHUR_PTS
-#define PBA_SCHUR_PTS 128
-#endif
-constexpr int SCHUR_PTS = PBA_SCHUR_PTS;   // points per Schur chunk (-DPBA_SCHUR_PTS: A/B builds)
-constexpr int SCHUR_W = 2048;    // points × local poses per Schur chunk (LDS budget: dynamic, 48 B each)
-
-enum : int { C_TRANSPOSE = 1, C_SCHUR = 2 };
 
 // kDoneDesync (multi-GPU): the ranks' decisions of the previous trial differed (kLmDesync = 1 + the number of ranks whose
 // record said done then); every rank ends the solve with an error
@@ -81,8 +75,6 @@ __device__ inline double decision_word(const double* lm) {
 #endif
 constexpr int kRecRing = PBA_REC_RING, kRecStride = kLmFields + 1;  // (-DPBA_REC_RING=1: the one-slot record, tests)
 __host__ __device__ inline long long rec_slot(double seq) { return ((long long)seq % kRecRing) * kRecStride; }
-// λ of a kernel: the record's (pba_gn.h, LmView), or — NaN there, host-driven steps — the kernel's argument
-__device__ __forceinline__ double lm_lambda(const LmView& v, double lambda) { return isnan(v.lambda) ? lambda : v.lambda; }
 
 struct SchurArgs {
   const int4* desc;       // first GN point, n points, n local poses, partial offset (doubles)
@@ -603,7 +595,6 @@ __global__ void assemble_kernel(AsmArgs a, double lambda) {
 // Multi-GPU exchange (include/pba.h): this rank's partial reduced system in the banded exchange layout,
 // and the finalisation of the summed system into the band solvers' input.
 // ------------------------------------------------------------------------------------------------
-constexpr int EX_TAIL = 24;  // g(6) | g_direct(6) | diag(A)(6) | observed | pad
 __host__ __device__ constexpr long long ex_row(int K) { return (long long)(K + 1) * 36 + EX_TAIL; }
 
 // One lane per element of the exchange buffer (the local skyline's elements by the contribution lists of
@@ -855,11 +846,6 @@ __device__ __forceinline__ void wg_reduce_sum_max(double (&v)[N], double m, doub
     *dst = x;
   }
 }
-
-// ib_data per GN block (free intrinsics, intr_rows_kernel): weighted fp64 rows J_i (2×8) | J_h (2×6) | J_t (2×6) | J_ρ (2) |
-// r (2), and W_i = J_iᵀJ_ρ (8)
-constexpr int kIbStride = 52;
-constexpr int kIbJi = 0, kIbJh = 16, kIbJt = 28, kIbJr = 40, kIbR = 42, kIbWi = 44;
 
 // The update workgroups' partials besides the model decrease (slot layout of red): Σ|x − x_new|² and Σ|x_new|² in the
 // ambient parameter space (red2, two doubles per slot: Ceres' step_norm and x_norm, trust_region_minimizer.cc:706-726,
@@ -1183,660 +1169,6 @@ __global__ __launch_bounds__(kBlockThreads) void update_kernel(const PoseUpdateA
     camera_kf(tk, r.kf);
     ra.pairs_new[i] = r;
   }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Free intrinsics in the reduced camera system (pba_set_optimize_intrinsics; geometric engines)
-// ------------------------------------------------------------------------------------------------
-// bundle_adjustment() with BundleAdjustmentOptions::optimize_intrinsics leaves the cameras' 8-vector intrinsics blocks
-// free (map_utils.h:339-345); the functor differentiates the TARGET camera's intrinsics (reprojection.h:83-86, :108) and
-// SPARSE_SCHUR keeps those blocks among the f-blocks of the reduced camera system (schur_complement_solver.cc:138-146).
-// Here camera c's intrinsics are the system frames nf + 2c (dims 0-5) and nf + 2c + 1 (dims 6-7, then four identity
-// pads): a dense border of the skyline system (their profile starts at frame 0).  The keyframe part is linearised,
-// eliminated and assembled as without intrinsics; the border — the blocks' direct terms J_iᵀJ_x and the points' Schur
-// terms −W_i,c W_xᵀ / H'_ρρ — is formed in fp64 by the border kernels below (a wave per keyframe block, camera blocks
-// split over workgroups) in a fixed order (the CSR lists of gn_prepare), from weighted fp64 rows (intr_rows_kernel) and
-// schur_kernel's undamped H_ρρ; on several GPUs each rank exports its border rows undamped (import_sky_kernel sums them).
-struct IntrRowsArgs {
-  const int4* rec;       // GN block → {block, point, host, target}
-  const double* poses;
-  const double* rho;
-  const double2* u_ref;
-  const double2* u_obs;
-  const int* frame_cam;
-  const double* cams;    // host unprojection: the cameras (the functor's captured intrinsics, reprojection.h:93-98)
-  const double* kt;      // target projection: the intrinsics state (camera records)
-  double huber;
-  double* out;           // ib_data
-  int n;
-  const double* lm;      // LM record: nothing to do once the solve is done
-  // point-aligned waves (gn_prepare, every GN point ≤ 64 blocks): wave w takes GN blocks wave_tab[w].x … + .y − 1, whole
-  // points from GN point wave_tab[w].z on, and also writes their W sums into pw (intr_pw_kernel's work); else nullptr
-  const int4* wave_tab = nullptr;
-  int n_waves = 0;
-  double* pw = nullptr;
-  int nc = 0;
-};
-struct PoseT {  // a relative pose for pair_rotation / pair_translation
-  double R[9], t[3];
-  float Rf[9], tf[3];
-};
-
-// One lane per GN block at the current state: r = u_obs − π_t(T_th b/ρ) and its Jacobians (the geometric_row chain, in
-// fp64), J_i = −∂π/∂k (project_intr_jac), Ceres' Corrector weighting √ρ' (corrector.cc, ρ'' ≤ 0 for Huber), W_i = J_iᵀJ_ρ.
-// The rows leave through LDS (PBA_IB_DIRECT: straight from the lanes): a lane's 416-B row stored from registers is 26
-// 16-B stores 416 B apart per instruction — 64 partial lines each — so each wave stages its 64 rows in two halves of 26
-// doubles and stores every half as the 13 16-B chunks of each row, consecutive lanes on consecutive chunks.
-#ifndef PBA_IB_DIRECT
-constexpr int kIbStage = 27;  // doubles per staged half row (26 used; odd: 2-way LDS bank conflicts at most)
-#endif
-template <int MODEL>
-__global__ __launch_bounds__(256) void intr_rows_kernel(const IntrRowsArgs a) {
-  const int lane = threadIdx.x & 63;
-#ifdef PBA_IB_DIRECT
-  const int gb0 = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gb0 >= a.n || lm_view(a.lm).done != 0.0) return;
-  const int gb = gb0;
-#else
-  // the wave's rows: 64 consecutive GN blocks, or (wave_tab) a point-aligned run of ≤ 64
-  int row0, nrow;
-  int4 wt = make_int4(0, 0, 0, 0);
-  if (a.wave_tab) {
-    const int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (w >= a.n_waves) return;  // (whole waves)
-    wt = a.wave_tab[w];
-    row0 = wt.x;
-    nrow = wt.y;
-  } else {
-    row0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63);
-    nrow = min(64, a.n - row0);
-    if (nrow <= 0) return;  // (whole waves: the last workgroup's waves past the end — rec has a.n entries)
-  }
-  if (lm_view(a.lm).done != 0.0) return;       // (uniform)
-  const int gb = row0 + max(min(lane, nrow - 1), 0);  // every lane of a wave takes part in its stores
-#endif
-  const int4 br = a.rec[gb];
-  PoseT T;
-  pair_rotation(a.poses + 7 * br.z, a.poses + 7 * br.w, T);
-  pair_translation(a.poses + 7 * br.z, a.poses + 7 * br.w, T);
-  const int hc = a.frame_cam[br.z], tc = a.frame_cam[br.w];
-  const double* kt = a.kt + kCamD * tc;
-  const double2 ur = a.u_ref[br.y], uo = a.u_obs[br.x];
-  const double irho = 1.0 / a.rho[br.y];
-  const Vec3d b = unproject<MODEL>(a.cams + kCamD * hc + kCamHk, ur.x, ur.y);
-  const Vec3d ph = {b.x * irho, b.y * irho, b.z * irho};
-  const Vec3d Rp = mat_mul(T.R, ph);
-  const Vec3d p = {Rp.x + T.t[0], Rp.y + T.t[1], Rp.z + T.t[2]};
-  double u, v;
-  const double iden = project<MODEL>(kt, p, u, v);
-  double J[kIbStride];
-  J[kIbR] = uo.x - u;
-  J[kIbR + 1] = uo.y - v;
-  Vec3d du, dv;
-  project_jac<MODEL>(kt, p, iden, du, dv);
-  double ku[8], kv[8];
-  project_intr_jac<MODEL>(kt, p, iden, ku, kv);
-  const Vec3d td = {T.t[0], T.t[1], T.t[2]};
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const Vec3d d = i == 0 ? du : dv;
-    const Vec3d g = {-d.x, -d.y, -d.z};  // ∂r/∂p = −∂π/∂p
-    const Vec3d gR = row_mul(g, T.R);
-    const Vec3d wh = cross(ph, gR);
-    const Vec3d wt = cross(g, p);
-    double* jh = J + kIbJh + 6 * i;
-    double* jt = J + kIbJt + 6 * i;
-    jh[0] = gR.x; jh[1] = gR.y; jh[2] = gR.z; jh[3] = wh.x; jh[4] = wh.y; jh[5] = wh.z;
-    jt[0] = -g.x; jt[1] = -g.y; jt[2] = -g.z; jt[3] = wt.x; jt[4] = wt.y; jt[5] = wt.z;
-    J[kIbJr + i] = dot(g, td) * irho;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) J[kIbJi + 8 * i + j] = -(i == 0 ? ku[j] : kv[j]);
-  }
-  bool ok = true;
-#pragma unroll
-  for (int q = 0; q < kIbWi; ++q) ok = ok && isfinite(J[q]);
-  const double s2 = J[kIbR] * J[kIbR] + J[kIbR + 1] * J[kIbR + 1], hb = a.huber;
-  const double w = (hb <= 0.0 || s2 <= hb * hb) ? 1.0 : hb / sqrt(s2);
-  const double sw = ok ? sqrt(w) : 0.0;
-#pragma unroll
-  for (int q = 0; q < kIbWi; ++q) J[q] = ok ? sw * J[q] : 0.0;
-#pragma unroll
-  for (int d = 0; d < 8; ++d) J[kIbWi + d] = J[kIbJi + d] * J[kIbJr] + J[kIbJi + 8 + d] * J[kIbJr + 1];
-#ifdef PBA_IB_DIRECT
-  double* o = a.out + (long long)gb * kIbStride;
-#pragma unroll
-  for (int q = 0; q < kIbStride; q += 2) *reinterpret_cast<double2*>(o + q) = make_double2(J[q], J[q + 1]);
-#else
-  constexpr int HALF = kIbStride / 2, CH = HALF / 2;  // 26 doubles, 13 chunks of 16 B per half row
-  __shared__ double stage[4][64 * kIbStage];
-  double* st = stage[threadIdx.x >> 6];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-#pragma unroll
-    for (int q = 0; q < HALF; ++q) st[lane * kIbStage + q] = J[HALF * h + q];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-    for (int c0 = 0; c0 < 64 * CH; c0 += 64) {
-      const int c = c0 + lane, r = c / CH, j = c - CH * r;
-      if (r < nrow)
-        *reinterpret_cast<double2*>(a.out + (long long)(row0 + r) * kIbStride + HALF * h + 2 * j) =
-            make_double2(st[r * kIbStage + 2 * j], st[r * kIbStage + 2 * j + 1]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // this half's reads before the next half's writes
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  if (!a.wave_tab) return;
-  // the points' W sums (intr_pw_kernel's, in the same block order): each block's W_i, J_hᵀJ_ρ and camera through the
-  // stage, then the first block of every point adds its point's blocks
-  const int cam = a.frame_cam[br.w];
-#pragma unroll
-  for (int d = 0; d < 8; ++d) st[lane * kIbStage + d] = J[kIbWi + d];
-#pragma unroll
-  for (int k = 0; k < 6; ++k)
-    st[lane * kIbStage + 8 + k] = J[kIbJh + k] * J[kIbJr] + J[kIbJh + 6 + k] * J[kIbJr + 1];
-  st[lane * kIbStage + 14] = (double)cam;
-  const bool live = lane < nrow;
-  const int prev_pt = __shfl(br.y, (lane + 63) & 63, 64);
-  const unsigned long long firsts = __ballot(live && (lane == 0 || br.y != prev_pt));
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  if (!((firsts >> lane) & 1ull)) return;
-  const unsigned long long later = lane == 63 ? 0ull : firsts >> (lane + 1);
-  const int nb = later ? __builtin_ctzll(later) + 1 : nrow - lane;  // this point's blocks: lanes lane … lane + nb − 1
-  const int gp = wt.z + __popcll(firsts & ((1ull << lane) - 1ull));
-  double* o = a.pw + (long long)gp * (8 * a.nc + 6);
-  double wh[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int c0 = 0; c0 < a.nc; c0 += 4) {  // cameras in groups of four, as intr_pw_kernel
-    double wc[4][8];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int d = 0; d < 8; ++d) wc[c][d] = 0.0;
-    for (int b = lane; b < lane + nb; ++b) {
-      const double* sb = st + b * kIbStage;
-      const int cb = (int)sb[14] - c0;
-#pragma unroll
-      for (int d = 0; d < 8; ++d) {
-        const double w = sb[d];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) wc[c][d] += c == cb ? w : 0.0;
-      }
-      if (c0 == 0)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) wh[k] += sb[8 + k];
-    }
-    for (int c = 0; c < 4 && c0 + c < a.nc; ++c)
-#pragma unroll
-      for (int d = 0; d < 8; ++d) o[8 * (c0 + c) + d] = wc[c][d];
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) o[8 * a.nc + k] = wh[k];
-#endif
-}
-
-struct IntrBorderArgs {
-  const double* ib;        // ib_data
-  const int4* ib_rec;      // GN block → {block, point, host, target}
-  const int* ib_cam;       // GN block → its target's camera
-  const int4* pt_rec;      // GN point → {first GN block, block count, host, point}
-  const double* pt_data;   // GN point → [H_ρρ (undamped), g_ρ, …] (schur_kernel of this solve)
-  const int* bptr;         // border unit pair (c, u) = c·(nf + nc) + u → direct-term GN blocks …
-  const int* blist;        // (keyframe units: bit 31 set when the keyframe hosts the block)
-  const int* pptr;         // … and Schur-term GN points
-  const int* plist;
-  const int* sky_first;
-  const int* sky_row;
-  const uint8_t* fixed;    // system frames
-  const double* lm;
-  double* S;
-  double* g;
-  double* g_dir;
-  double* Ddiag;
-  int nf, nc;
-  double* X = nullptr;     // multi-GPU export (pba_gn_step_export): this rank's border rows, undamped, into the exchange
-  long long xs = 0;        // buffer's border region (row stride nfs·36 + EX_TAIL) instead of S
-  const double* pw = nullptr;  // GN point → its camera sums W_c (8 per camera) and W_h = Σ J_hᵀJ_ρ (6): intr_pw_kernel
-  const int* pblk = nullptr;   // per plist entry of a keyframe unit: −1 the keyframe hosts the point, else the point's
-                               // one block targeting it (−2: several — walk the point's blocks)
-};
-
-// Per GN point, over its blocks in order: W_c = Σ_{b: camera(b) = c} W_i(b) for every camera c, and W_h = Σ_b J_h(b)ᵀJ_ρ(b)
-// (every block of a point has the point's host).  The border kernels' Schur terms read these 8·nc + 6 values instead of
-// walking the point's blocks (4-5 × 52 doubles) once per (point, list) — at C4 that walk re-read the blocks' rows five
-// times per kernel, ≈ 0.4 GB per launch.  The same sums in the same order: the border is unchanged bit for bit.
-__global__ __launch_bounds__(256) void intr_pw_kernel(const IntrBorderArgs a, int n_points) {
-  // 8 lanes per point: lane k sums component k of every camera's W_c and (k < 6) of W_h, over the blocks in order
-  const int t = blockIdx.x * blockDim.x + threadIdx.x, gp = t >> 3, k = t & 7;
-  if (gp >= n_points) return;
-  const int4 pr = a.pt_rec[gp];
-  const int st = 8 * a.nc + 6;
-  double* o = const_cast<double*>(a.pw) + (long long)gp * st;
-  double wh = 0.0;
-  for (int c0 = 0; c0 < a.nc; c0 += 4) {  // cameras in groups of four (one pass over the blocks per group)
-    double wc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int b = pr.x; b < pr.x + pr.y; ++b) {
-      const double* B = a.ib + (long long)b * kIbStride;
-      const int cb = a.ib_cam[b] - c0;
-      const double w = B[kIbWi + k];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) wc[c] += c == cb ? w : 0.0;
-      if (c0 == 0 && k < 6) wh += B[kIbJh + k] * B[kIbJr] + B[kIbJh + 6 + k] * B[kIbJr + 1];
-    }
-    for (int c = 0; c < 4 && c0 + c < a.nc; ++c) o[8 * (c0 + c) + k] = wc[c];
-  }
-  if (k < 6) o[8 * a.nc + k] = wh;
-}
-
-// Element t of border row `row` (system frame P = nf + row): t < (P + 1)·36 → entry (r, cc) of block (P, y = t / 36) of
-// the skyline system; t = nfs·36 … nfs·36 + 5 → g of P.  The keyframe blocks (P, x < nf) and the camera blocks (P, y ≥ nf)
-// get direct − Schur terms, + λ·clamp(diag) on the diagonal (the direct part is Ceres' LM diagonal), identity pads, and
-// — constant frames / unobserved cameras — identity rows and columns, as assemble_kernel.  border_store writes element t
-// from its two totals (direct, Schur).
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ double border_inv(const IntrBorderArgs& a, int gp, double lambda) {
-  const double H = a.pt_data[(long long)gp * 8];
-  const double Hd = H + lambda * fmin(fmax(H, 1e-6), 1e32);
-  return Hd > 0.0 ? 1.0 / Hd : 0.0;
-}
-__device__ __forceinline__ void border_store(const IntrBorderArgs& a, double lambda, int row, int t, double dir,
-                                             double sch) {
-  const int P = a.nf + row, nfs = a.nf + 2 * a.nc, h = row & 1;
-  if (a.X) {  // export: direct − Schur, the direct diagonal, g, the direct gradient, observed (import_sky_kernel damps,
-              // pads and fixes the summed rows)
-    double* xr = a.X + (long long)row * a.xs;
-    double* tail = xr + (long long)nfs * 36;
-    if (t >= nfs * 36) {
-      const int r = t - nfs * 36;
-      tail[r] = dir - sch;
-      tail[6 + r] = dir;
-      if (r == 0) tail[18] = a.fixed[P] ? 0.0 : 1.0;  // a camera this rank observes
-      return;
-    }
-    const int y = t / 36, e = t % 36, r = e / 6, cc = e % 6, d = 6 * h + r;
-    const int d2 = y >= a.nf ? 6 * ((y - a.nf) & 1) + cc : cc;
-    const bool pad = d >= 8 || d2 >= 8;
-    xr[(long long)y * 36 + e] = pad ? 0.0 : dir - sch;
-    if (y == P && r == cc) tail[12 + r] = pad ? 0.0 : dir;
-    return;
-  }
-  if (t >= nfs * 36) {
-    const int r = t - nfs * 36;
-    const bool fx = a.fixed[P] != 0;
-    a.g[6 * P + r] = fx ? 0.0 : dir - sch;
-    a.g_dir[6 * P + r] = fx ? 0.0 : dir;
-    if (fx) a.Ddiag[6 * P + r] = 0.0;
-    return;
-  }
-  const int y = t / 36, e = t % 36, r = e / 6, cc = e % 6, d = 6 * h + r;
-  const bool cam = y >= a.nf;
-  const int d2 = cam ? 6 * ((y - a.nf) & 1) + cc : cc;
-  if (d >= 8 || d2 >= 8) {  // pad
-    dir = (y == P && r == cc) ? 1.0 : 0.0;
-    sch = 0.0;
-  }
-  double val = dir - sch;
-  if (a.fixed[P] || a.fixed[y]) {
-    val = (y == P && r == cc) ? 1.0 : 0.0;
-  } else if (y == P && r == cc) {
-    const double D = fmin(fmax(dir, 1e-6), 1e32);  // levenberg_marquardt_strategy.cc: the undamped JᵀJ diagonal
-    a.Ddiag[6 * P + r] = D;
-    val += lambda * D;
-  }
-  a.S[((long long)a.sky_row[P] + (y - a.sky_first[P])) * 36 + e] = val;
-}
-
-// Σ over the wave of 48 per-lane values v[0 … 47] by recursive halving (a reduce-scatter: 24 + 12 + 6 + 3 + 6 shuffles
-// instead of 48 six-step butterflies): after the xor-32 / 16 / 8 / 4 steps lane l holds partial sums of the three values
-// base(l) … base(l) + 2, base = 24·b5 + 12·b4 + 6·b3 + 3·b2 of l's bits, completed over its quad by xor 2 and xor 1 (a + b
-// and b + a: the quad's lanes agree bit for bit).  Returns the total of value *vi = base(l) + (l & 3) for l & 3 < 3
-// (*vi = −1 and 0 otherwise).  A fixed order.
-__device__ __forceinline__ double wave_rs48(const double (&v)[48], int lane, int* vi) {
-  double a24[24], a12[12], a6[6], a3[3];
-  const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8, h2 = lane & 4;
-#pragma unroll
-  for (int i = 0; i < 24; ++i) a24[i] = (h5 ? v[24 + i] : v[i]) + __shfl_xor(h5 ? v[i] : v[24 + i], 32, 64);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) a12[i] = (h4 ? a24[12 + i] : a24[i]) + __shfl_xor(h4 ? a24[i] : a24[12 + i], 16, 64);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) a6[i] = (h3 ? a12[6 + i] : a12[i]) + __shfl_xor(h3 ? a12[i] : a12[6 + i], 8, 64);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) a3[i] = (h2 ? a6[3 + i] : a6[i]) + __shfl_xor(h2 ? a6[i] : a6[3 + i], 4, 64);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    a3[i] += __shfl_xor(a3[i], 2, 64);
-    a3[i] += __shfl_xor(a3[i], 1, 64);
-  }
-  const int j = lane & 3;
-  *vi = j < 3 ? 24 * h5 + 12 * h4 + 6 * h3 + 3 * h2 + j : -1;
-  return j == 0 ? a3[0] : j == 1 ? a3[1] : j == 2 ? a3[2] : 0.0;
-}
-
-// The keyframe blocks (P, y < nf) of both border rows of a camera: kpw WAVES per keyframe y (grid x: 4/kpw keyframes per
-// workgroup; y: camera c) form the 8 × 6 live entries of (2c, y) and (2c + 1, y) — row 2c + 1's frame holds intrinsics 6,
-// 7 and four pads — at once: a lane takes every (64·kpw)th entry of the keyframe's lists (its blocks and points seen by
-// the camera), each wave adds its lanes' sums (wave_rs48) and the kpw waves' sums are added in order (a fixed order).
-// kpw = 4 while the keyframe waves would not fill the SIMDs (C3, 200 keyframes), else 2 (C4: 2008 waves; 1 and 4 measured
-// 80.5 and 82.4 against 76.5 µs).  Round 5 walked the lists twice (one kernel per border row: 133 + 117 µs at C4) and
-// each point's blocks once per (point, list).
-__device__ __forceinline__ void border_keyframes(const IntrBorderArgs& a, double lambda, int kpw, int bx, int by) {
-  __shared__ double2 s_w[4][48];
-  lambda = lm_lambda(lm_view(a.lm), lambda);
-  const int c = by, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int gw = bx * 4 + w, y0 = gw / kpw, sub = gw % kpw;
-  const int y = min(y0, a.nf - 1);  // (a wave past the last keyframe walks nothing and stores nothing)
-  const int L = c * (a.nf + a.nc) + y;
-  const int q0 = sub * 64 + lane, dq = y0 < a.nf ? 64 * kpw : 1 << 30;
-  // the 8 intrinsics rows d of camera c (border rows 2c: d = 0…5, 2c + 1: d = 6, 7) × the keyframe's 6 columns, value
-  // v = 6d + cc; the direct terms first, then the Schur terms in the same registers; lane l ends with value vi (wave_rs48)
-  double acc[8][6];
-#pragma unroll
-  for (int d = 0; d < 8; ++d)
-#pragma unroll
-    for (int cc = 0; cc < 6; ++cc) acc[d][cc] = 0.0;
-  // the next entry's list index is loaded during this one (a list walk was two dependent memory rounds per entry: the
-  // index, then the row — and the host / target test on the block record before the row's Jacobian)
-  const int qb = a.bptr[L + 1];
-  int q = a.bptr[L] + (y0 < a.nf ? q0 : 1 << 30);
-  int bn = q < qb ? a.blist[q] : 0;
-  for (; q < qb; q += dq) {
-    const int bf = bn;
-    if (q + dq < qb) bn = a.blist[q + dq];
-    const double* B = a.ib + (long long)(bf & 0x7fffffff) * kIbStride;
-    const double* Jc = B + (bf < 0 ? kIbJh : kIbJt);
-    double c0[6], c1[6];
-#pragma unroll
-    for (int cc = 0; cc < 6; ++cc) {
-      c0[cc] = Jc[cc];
-      c1[cc] = Jc[6 + cc];
-    }
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      const double j0 = B[kIbJi + d], j1 = B[kIbJi + 8 + d];
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) acc[d][cc] += j0 * c0[cc] + j1 * c1[cc];
-    }
-  }
-  int vi;
-  double vd = wave_rs48(reinterpret_cast<const double(&)[48]>(acc), lane, &vi);
-#pragma unroll
-  for (int d = 0; d < 8; ++d)
-#pragma unroll
-    for (int cc = 0; cc < 6; ++cc) acc[d][cc] = 0.0;
-  const int qp = a.pptr[L + 1];
-  q = a.pptr[L] + (y0 < a.nf ? q0 : 1 << 30);
-  int gpn = q < qp ? a.plist[q] : 0, byn = q < qp ? a.pblk[q] : -1;
-  for (; q < qp; q += dq) {
-    const int gp = gpn, by = byn;
-    if (q + dq < qp) {
-      gpn = a.plist[q + dq];
-      byn = a.pblk[q + dq];
-    }
-    double wc[8], wy[6];  // W of the point for camera c (Σ W_i over its blocks seen by c, intr_pw_kernel) and for
-                          // keyframe y (Σ J_h / J_t ᵀJ_ρ over its blocks hosted / targeted by y)
-    const double* pw = a.pw + (long long)gp * (8 * a.nc + 6);
-#pragma unroll
-    for (int d = 0; d < 8; ++d) wc[d] = pw[8 * c + d];
-    if (by == -1) {  // y hosts the point: every block's J_hᵀJ_ρ (intr_pw_kernel)
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) wy[cc] = pw[8 * a.nc + cc];
-    } else if (by >= 0) {  // y is a target: the point's block targeting it
-      const double* B = a.ib + (long long)by * kIbStride;
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) wy[cc] = 0.0 + (B[kIbJt + cc] * B[kIbJr] + B[kIbJt + 6 + cc] * B[kIbJr + 1]);
-    } else {  // several blocks of the point target y: their sum, in block order
-      const int4 pr = a.pt_rec[gp];
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) wy[cc] = 0.0;
-      for (int b = pr.x; b < pr.x + pr.y; ++b) {
-        if (a.ib_rec[b].w != y) continue;
-        const double* B = a.ib + (long long)b * kIbStride;
-#pragma unroll
-        for (int cc = 0; cc < 6; ++cc) wy[cc] += B[kIbJt + cc] * B[kIbJr] + B[kIbJt + 6 + cc] * B[kIbJr + 1];
-      }
-    }
-    const double inv = border_inv(a, gp, lambda);
-#pragma unroll
-    for (int d = 0; d < 8; ++d)
-#pragma unroll
-      for (int cc = 0; cc < 6; ++cc) acc[d][cc] += inv * wc[d] * wy[cc];
-  }
-  double vs = wave_rs48(reinterpret_cast<const double(&)[48]>(acc), lane, &vi);
-  if (kpw > 1) {  // the keyframe's kpw waves, in order
-    if (vi >= 0) s_w[w][vi] = make_double2(vd, vs);
-    __syncthreads();
-    if (sub == 0 && vi >= 0) {
-      double2 t = s_w[w][vi];
-      for (int k = 1; k < kpw; ++k) {
-        t.x += s_w[w + k][vi].x;
-        t.y += s_w[w + k][vi].y;
-      }
-      vd = t.x;
-      vs = t.y;
-    }
-    if (sub != 0) return;  // (whole waves)
-  }
-  // row 2c: values 0 … 35 (element v); row 2c + 1: values 36 … 47 (d = 6, 7) as its elements 0 … 11, its elements
-  // 12 … 35 pads (border_store) from lanes 12 … 35
-  if (y0 < a.nf) {
-    if (vi >= 0) border_store(a, lambda, vi < 36 ? 2 * c : 2 * c + 1, y * 36 + (vi < 36 ? vi : vi - 36), vd, vs);
-    if (lane >= 12 && lane < 36) border_store(a, lambda, 2 * c + 1, y * 36 + lane, 0.0, 0.0);
-  }
-}
-
-// The camera blocks (P = nf + 2c + h, y = nf + 2c2 + h2 ≥ nf, c2 ≤ c) and the gradient rows of the border, as two
-// reductions over whole lists instead of one list walk per (border row, column block) — the list of a camera holds ALL
-// of its blocks (400k at C4) and points (100k), and round 5 walked it six times per trial (two row kernels × three column
-// blocks, 165 µs at C4 with the finishing kernel):
-//   cam_dir — per camera c, over its blocks: Σ J_iᵀJ_i (the 8 × 8 upper triangle, 36) and Σ J_iᵀr (8): the
-//     direct terms (a block's intrinsics Jacobian is its target camera's, so the direct part couples a camera only with
-//     itself);
-//   cam_sch — per camera pair (c, c2 ≤ c), over the points seen by both: Σ_p W_c W_c2ᵀ / H'_ρρ (8 × 8) and,
-//     for c2 = c, Σ_p W_c g_ρ / H'_ρρ (8): the Schur terms (W_c from intr_pw_kernel);
-// each over kCamSplit workgroups (a thread takes every (256·kCamSplit)th entry; wave butterflies, then the four waves in
-// order), and intr_cam_fin_kernel adds the kCamSplit totals in order per element and stores it (border_store) — a fixed
-// order end to end.
-constexpr int kCamSplit = 128;  // (512 measured no faster at C4, 2.7× slower for two cameras' Schur sums at C3)
-constexpr int kCamDir = 44, kCamSch = 72;  // accumulators per thread
-
-__device__ __forceinline__ int upper8i(int i, int j) { return i * 8 - i * (i - 1) / 2 + (j - i); }  // i ≤ j < 8
-
-// Σ over the wave of N per-lane values (N a multiple of 16) into dst[0 … N) by recursive halving, as wave_rs48: after the
-// xor-32 / 16 / 8 / 4 steps lane l holds partial sums of values base(l) … base(l) + N/16 − 1 (base = N/2·b5 + N/4·b4 +
-// N/8·b3 + N/16·b2), completed over its quad by xor 2 and xor 1; the quad's lanes store them.  A fixed order.
-template <int N>
-__device__ __forceinline__ void wave_rs_lds(const double (&v)[N], int lane, double* dst) {
-  static_assert(N % 16 == 0, "four halvings");
-  constexpr int H1 = N / 2, H2 = N / 4, H3 = N / 8, H4 = N / 16;
-  double a1[H1], a2[H2], a3[H3], a4[H4];
-  const bool h5 = lane & 32, h4 = lane & 16, h3 = lane & 8, h2 = lane & 4;
-#pragma unroll
-  for (int i = 0; i < H1; ++i) a1[i] = (h5 ? v[H1 + i] : v[i]) + __shfl_xor(h5 ? v[i] : v[H1 + i], 32, 64);
-#pragma unroll
-  for (int i = 0; i < H2; ++i) a2[i] = (h4 ? a1[H2 + i] : a1[i]) + __shfl_xor(h4 ? a1[i] : a1[H2 + i], 16, 64);
-#pragma unroll
-  for (int i = 0; i < H3; ++i) a3[i] = (h3 ? a2[H3 + i] : a2[i]) + __shfl_xor(h3 ? a2[i] : a2[H3 + i], 8, 64);
-#pragma unroll
-  for (int i = 0; i < H4; ++i) a4[i] = (h2 ? a3[H4 + i] : a3[i]) + __shfl_xor(h2 ? a3[i] : a3[H4 + i], 4, 64);
-  const int base = H1 * h5 + H2 * h4 + H3 * h3 + H4 * h2;
-#pragma unroll
-  for (int i = 0; i < H4; ++i) {
-    a4[i] += __shfl_xor(a4[i], 2, 64);
-    a4[i] += __shfl_xor(a4[i], 1, 64);
-    if ((i & 3) == (lane & 3)) dst[base + i] = a4[i];
-  }
-}
-constexpr int pad16(int n) { return (n + 15) / 16 * 16; }
-
-// Σ over the workgroup of NV per-thread accumulators in a fixed order → out[0 … NV): each wave's sums by wave_rs_lds
-// into s_w (4·pad16(NV) doubles), then the four waves in order.  Every thread calls it.
-template <int NV>
-__device__ __forceinline__ void wg_sum_store(const double* acc, double* s_w, double* out) {
-  constexpr int NP = pad16(NV);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  double v[NP];
-#pragma unroll
-  for (int i = 0; i < NP; ++i) v[i] = i < NV ? acc[i] : 0.0;
-  wave_rs_lds<NP>(v, lane, s_w + w * NP);
-  __syncthreads();
-  for (int i = threadIdx.x; i < NV; i += blockDim.x) out[i] = ((s_w[i] + s_w[NP + i]) + s_w[2 * NP + i]) + s_w[3 * NP + i];
-}
-
-__device__ __forceinline__ void cam_dir(const IntrBorderArgs& a, double* part, int bx, int by) {
-  __shared__ double s_w[4 * pad16(kCamDir)];
-  const int c = by, L = c * (a.nf + a.nc) + a.nf + c;  // (camera c, unit nf + c): every block of camera c
-  double acc[kCamDir];
-#pragma unroll
-  for (int v = 0; v < kCamDir; ++v) acc[v] = 0.0;
-  const int qe = a.bptr[L + 1];
-  int q = a.bptr[L] + threadIdx.x + 256 * bx;
-  int bn = q < qe ? a.blist[q] : 0;  // (the next entry's index loaded during this one)
-  for (; q < qe; q += 256 * kCamSplit) {
-    const double* B = a.ib + (long long)bn * kIbStride;
-    if (q + 256 * kCamSplit < qe) bn = a.blist[q + 256 * kCamSplit];
-    double j0[8], j1[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      j0[k] = B[kIbJi + k];
-      j1[k] = B[kIbJi + 8 + k];
-    }
-    const double r0 = B[kIbR], r1 = B[kIbR + 1];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-      for (int j = i; j < 8; ++j) acc[upper8i(i, j)] += j0[i] * j0[j] + j1[i] * j1[j];
-      acc[36 + i] += j0[i] * r0 + j1[i] * r1;
-    }
-  }
-  wg_sum_store<kCamDir>(acc, s_w, part + ((long long)c * kCamSplit + bx) * kCamDir);
-}
-
-__device__ __forceinline__ void cam_sch(const IntrBorderArgs& a, double lambda, double* part, int bx, int by) {
-  __shared__ double s_w[4 * pad16(kCamSch)];
-  lambda = lm_lambda(lm_view(a.lm), lambda);
-  const int pc = by;  // camera pair (c, c2 ≤ c), pc = c(c+1)/2 + c2
-  int c = 0;
-  while ((c + 1) * (c + 2) / 2 <= pc) ++c;
-  const int c2 = pc - c * (c + 1) / 2, L = c * (a.nf + a.nc) + a.nf + c2;  // points seen by c and c2
-  const int st = 8 * a.nc + 6;
-  double acc[kCamSch];
-#pragma unroll
-  for (int v = 0; v < kCamSch; ++v) acc[v] = 0.0;
-  for (int q = a.pptr[L] + threadIdx.x + 256 * bx; q < a.pptr[L + 1]; q += 256 * kCamSplit) {
-    const int gp = a.plist[q];
-    const double* pw = a.pw + (long long)gp * st;
-    const double inv = border_inv(a, gp, lambda), gr = a.pt_data[(long long)gp * 8 + 1];
-    double wc[8], w2[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      wc[k] = pw[8 * c + k];
-      w2[k] = pw[8 * c2 + k];
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const double iw = inv * wc[i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[8 * i + j] += iw * w2[j];
-      acc[64 + i] += iw * gr;
-    }
-  }
-  wg_sum_store<kCamSch>(acc, s_w, part + ((long long)pc * kCamSplit + bx) * kCamSch);
-}
-
-__global__ __launch_bounds__(256) void intr_border_kernel(const IntrBorderArgs a, double lambda, int kpw) {
-  border_keyframes(a, lambda, kpw, blockIdx.x, blockIdx.y);
-}
-__global__ __launch_bounds__(256) void intr_cam_dir_kernel(const IntrBorderArgs a, double* part) {
-  cam_dir(a, part, blockIdx.x, blockIdx.y);
-}
-__global__ __launch_bounds__(256) void intr_cam_sch_kernel(const IntrBorderArgs a, double lambda, double* part) {
-  cam_sch(a, lambda, part, blockIdx.x, blockIdx.y);
-}
-// The three border reductions are independent (they read the rows, the points' sums and the lists, and write
-// different outputs): while the keyframe part is small (nf·nc < 512 keyframe blocks, the 4-waves-per-keyframe regime:
-// C3), one launch runs them side by side — workgroups [0, nk) the keyframe blocks (nk_x per camera), then kCamSplit per
-// camera of direct sums, then kCamSplit per camera pair of Schur sums — instead of three launches in sequence, each a
-// fraction of the chip (C3: 35.3 → 24.6 µs, two cameras 41.3 → 31.1; at C4, where the keyframe part alone fills the
-// chip, side by side measured 108 against 102 µs in sequence).
-__global__ __launch_bounds__(256) void intr_border_all_kernel(const IntrBorderArgs a, double lambda, int kpw, int nk_x,
-                                                             double* dpart, double* spart) {
-  int b = blockIdx.x;
-  const int nk = nk_x * a.nc, nd = kCamSplit * a.nc;
-  if (b < nk) {
-    border_keyframes(a, lambda, kpw, b % nk_x, b / nk_x);
-    return;
-  }
-  b -= nk;
-  if (b < nd) {
-    cam_dir(a, dpart, b % kCamSplit, b / kCamSplit);
-    return;
-  }
-  b -= nd;
-  cam_sch(a, lambda, spart, b % kCamSplit, b / kCamSplit);
-}
-
-// One WAVE per (border row, camera column block yb ≤ row, entry e) and per border gradient element: lane l adds totals l,
-// l + 64, … of the kCamSplit in order, the wave's lanes by xor butterflies (a fixed order); then border_store.
-__device__ __forceinline__ void cam_fin(const IntrBorderArgs& a, double lambda, const double* dpart, const double* spart,
-                                        int blk) {
-  lambda = lm_lambda(lm_view(a.lm), lambda);
-  const int nb = 2 * a.nc + 1, i = blk * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (i >= 2 * a.nc * nb * 36) return;
-  const int e = i % 36, yb = (i / 36) % nb, row = i / (36 * nb);
-  const bool grad = yb == 2 * a.nc;
-  if (grad ? (e % 6 != 0) : (yb > row)) return;  // (the upper camera blocks are not stored; whole waves)
-  const int c = row >> 1, h = row & 1, r = e / 6, cc = e % 6, d = 6 * h + r;
-  auto sum = [&](const double* p, int stride, int idx) {
-    double v = 0.0;
-    for (int s = lane; s < kCamSplit; s += 64) v += p[(long long)s * stride + idx];
-    return wave_sum(v);
-  };
-  double dir = 0.0, sch = 0.0;
-  if (grad) {
-    if (d < 8) {
-      dir = sum(dpart + (long long)c * kCamSplit * kCamDir, kCamDir, 36 + d);
-      sch = sum(spart + (long long)(c * (c + 1) / 2 + c) * kCamSplit * kCamSch, kCamSch, 64 + d);
-    }
-    if (lane == 0) border_store(a, lambda, row, (a.nf + 2 * a.nc) * 36 + r, dir, sch);
-    return;
-  }
-  const int c2 = yb >> 1, d2 = 6 * (yb & 1) + cc;
-  if (d < 8 && d2 < 8) {  // (pads: border_store's identity rows)
-    if (c2 == c) dir = sum(dpart + (long long)c * kCamSplit * kCamDir, kCamDir, upper8i(min(d, d2), max(d, d2)));
-    sch = sum(spart + (long long)(c * (c + 1) / 2 + c2) * kCamSplit * kCamSch, kCamSch, 8 * d + d2);
-  }
-  if (lane == 0) border_store(a, lambda, row, (a.nf + yb) * 36 + e, dir, sch);
-}
-__global__ __launch_bounds__(256) void intr_cam_fin_kernel(const IntrBorderArgs a, double lambda, const double* dpart,
-                                                          const double* spart) {
-  cam_fin(a, lambda, dpart, spart, blockIdx.x);
-}
-// The same, with the arrow solve's level 0 (arrow_build) in workgroups fin_blocks … of the same launch: it reads the
-// keyframe band and g (assemble_kernel) and the border rows' keyframe blocks (border_keyframes), nothing this launch
-// writes — one launch fewer per trial.
-__global__ __launch_bounds__(256) void intr_cam_fin_build_kernel(const IntrBorderArgs a, double lambda,
-                                                                const double* dpart, const double* spart,
-                                                                const ArrowArgs aa, int batches, int fin_blocks) {
-  if ((int)blockIdx.x < fin_blocks) cam_fin(a, lambda, dpart, spart, blockIdx.x);
-  else arrow_build(aa, batches, (long long)(blockIdx.x - fin_blocks) * blockDim.x + threadIdx.x);
-}
-
-// The candidate intrinsics become the state (after an accepted trial; lm == nullptr: always), fp64 records and fp32 copy.
-__global__ void intr_accept_kernel(const double* __restrict__ lm, const double* __restrict__ knew_d,
-                                   const float* __restrict__ knew_f, double* __restrict__ k_d, float* __restrict__ k_f,
-                                   int nc) {
-  if (lm && (lm[kLmAccept] == 0.0 || lm[kLmDone] != 0.0)) return;
-  const int i = threadIdx.x, c = i >> 3, d = i & 7;
-  if (c >= nc) return;
-  k_d[kCamD * c + d] = knew_d[kCamD * c + d];
-  k_f[8 * c + d] = knew_f[8 * c + d];
 }
 
 __global__ __launch_bounds__(kBlockThreads) void cost_reduce_kernel(const float* cost, const uint8_t* valid, int n,
@@ -2370,7 +1702,20 @@ int gn_lpb(const pba_engine* e) { return e->opt.residual_kind == PBA_RESIDUAL_GE
 // rows per lane of the linearisation: 1 up to 8 px (one lane per row), ⌈P/8⌉ above (linearize_adj_kernel<·, PPL>)
 int gn_ppl(const pba_engine* e) { return e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC ? 1 : (e->P + 7) / 8; }
 
-// Symbolic analysis: GN block order, chunks, slot layouts, skyline profile and contribution lists.
+// A plan vector (pba_gn_plan.h) into its device buffer: the plan's records are the device's int4 / int2 / uchar2 byte
+// for byte.
+static_assert(sizeof(PlanInt4) == sizeof(int4) && sizeof(PlanInt2) == sizeof(int2) && sizeof(PlanUchar2) == sizeof(uchar2),
+              "the plan's records are uploaded as the device's vector types");
+template <class D, class H>
+hipError_t upload_plan(DevBuf<D>& buf, const std::vector<H>& h, hipStream_t s) {
+  static_assert(sizeof(D) == sizeof(H), "element for element");
+  const hipError_t rc = buf.resize(h.size());
+  if (rc != hipSuccess || h.empty()) return rc;
+  return hipMemcpyAsync(buf.p, h.data(), h.size() * sizeof(H), hipMemcpyHostToDevice, s);
+}
+
+// The symbolic analysis (build_gn_plan: GN block order, chunks, slot layouts, skyline profile, contribution and border
+// lists) into GnData, in upload order, and the buffers sized by it.
 int gn_prepare(pba_engine* e) {
   GnData& G = e->gn;
   const int nb = e->n_blocks, nf = e->n_frames;
@@ -2378,371 +1723,69 @@ int gn_prepare(pba_engine* e) {
   G.lpb = gn_lpb(e);
   G.ppl = gn_ppl(e);
   G.bpw = kBlockThreads / G.lpb;
-  const std::vector<int>& ph = e->point_host_h;
-  // GN order: (host, point, target)
-  std::vector<int> order(nb);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-    const int pa_ = e->block_point_h[a], pb_ = e->block_point_h[b];
-    if (ph[pa_] != ph[pb_]) return ph[pa_] < ph[pb_];
-    if (pa_ != pb_) return pa_ < pb_;
-    return e->block_target_h[a] < e->block_target_h[b];
-  });
-  std::vector<int> gtgt(nb);
-  for (int i = 0; i < nb; ++i) gtgt[i] = e->block_target_h[order[i]];
-  // linearise order: each host's GN range regrouped by target (stable), so a chunk's blocks of one target are
-  // consecutive (one matrix-core chain per target run in linearize_kernel)
-  std::vector<int> lpos(nb);
-  std::iota(lpos.begin(), lpos.end(), 0);
-  for (int i = 0; i < nb;) {
-    const int h = ph[e->block_point_h[order[i]]];
-    int j = i;
-    while (j < nb && ph[e->block_point_h[order[j]]] == h) ++j;
-    std::stable_sort(lpos.begin() + i, lpos.begin() + j, [&](int x, int y) { return gtgt[x] < gtgt[y]; });
-    i = j;
-  }
-  // linearise chunks
-  std::vector<int4> cdesc;
-  std::vector<uint8_t> blt(nb);
-  std::vector<std::vector<int>> chunk_targets;
-  std::vector<int> chunk_host;
-  size_t off = 0;
-  for (int i = 0; i < nb;) {
-    const int h = ph[e->block_point_h[order[lpos[i]]]];
-    int j = i;
-    std::vector<int> tg;
-    while (j < nb && j - i < G.bpw && ph[e->block_point_h[order[lpos[j]]]] == h) {
-      const int t = gtgt[lpos[j]];
-      auto it = std::find(tg.begin(), tg.end(), t);
-      if (it == tg.end() && (int)tg.size() == kChunkTargets) break;  // a chunk spans ≤ kChunkTargets targets
-      blt[j] = (uint8_t)(it - tg.begin());
-      if (it == tg.end()) tg.push_back(t);
-      ++j;
-    }
-    cdesc.push_back(make_int4(i, j - i, (int)tg.size(), (int)off));
-    off += SLOT_LIN_BASE + SLOT_LIN_T * tg.size();
-    chunk_targets.push_back(tg);
-    chunk_host.push_back(h);
-    i = j;
-  }
-  G.lin_slots = off;
-  G.n_chunks = (int)cdesc.size();
-  // GN points
-  std::vector<int> pfirst, pnblk, porig, phost;
-  for (int i = 0; i < nb;) {
-    const int p = e->block_point_h[order[i]];
-    int j = i;
-    while (j < nb && e->block_point_h[order[j]] == p) ++j;
-    pfirst.push_back(i);
-    pnblk.push_back(j - i);
-    porig.push_back(p);
-    phost.push_back(ph[p]);
-    i = j;
-  }
-  const int ngp = (int)pfirst.size();
-  G.n_gn_points = ngp;
-  // Schur chunks
-  G.schur_lds = 0;
-  std::vector<int4> sdesc;
-  std::vector<int4> saux;
-  std::vector<uchar2> spairs;
-  std::vector<int> lvp;
-  int max_nv = 1;
-  std::vector<std::vector<char>> schur_used_flag;
-  std::vector<uint8_t> blv(nb, 0);
-  std::vector<std::vector<int>> schur_poses;
-  std::vector<std::vector<std::pair<int, int>>> schur_used;
-  size_t soff = 0;
-  for (int p = 0; p < ngp;) {
-    const int h = phost[p];
-    std::vector<int> poses{h};
-    int q = p;
-    while (q < ngp && q - p < SCHUR_PTS && phost[q] == h) {
-      std::vector<int> add;
-      for (int b = pfirst[q]; b < pfirst[q] + pnblk[q]; ++b)
-        if (std::find(poses.begin(), poses.end(), gtgt[b]) == poses.end() &&
-            std::find(add.begin(), add.end(), gtgt[b]) == add.end())
-          add.push_back(gtgt[b]);
-      const int nv = (int)(poses.size() + add.size());
-      if (q > p && ((q - p + 1) * nv > SCHUR_W || nv > 255)) break;
-      if (nv > 255 || nv > SCHUR_W) return fail(PBA_ERR_INVALID_ARGUMENT, "a point observes too many keyframes");
-      poses.insert(poses.end(), add.begin(), add.end());
-      ++q;
-    }
-    const int nv = (int)poses.size();
-    std::vector<char> used(nv * nv, 0);
-    std::vector<int> lpair(nv, 0);  // the pair (host, poses[l]) of each local target
-    for (int r = p; r < q; ++r) {
-      std::vector<int> lv{0};
-      for (int b = pfirst[r]; b < pfirst[r] + pnblk[r]; ++b) {
-        const int l = (int)(std::find(poses.begin(), poses.end(), gtgt[b]) - poses.begin());
-        blv[b] = (uint8_t)l;
-        lpair[l] = e->pair_of_h[order[b]];
-        lv.push_back(l);
-      }
-      for (int x : lv)
-        for (int y : lv) used[std::min(x, y) * nv + std::max(x, y)] = 1;
-    }
-    // pair slots: the used pairs, or every pair (a ≤ b) in canonical order when the chunk takes the matrix-core path
-    // of schur_kernel (≤ 5 local poses; unused pairs are zero blocks no contribution list references)
-    const bool canon = nv * 6 + 1 <= 32;
-    std::vector<std::pair<int, int>> up;
-    std::vector<char> upu;
-    for (int x = 0; x < nv; ++x)
-      for (int y = x; y < nv; ++y)
-        if (canon || used[x * nv + y]) {
-          up.emplace_back(x, y);
-          upu.push_back(used[x * nv + y]);
-        }
-    const int fb0 = pfirst[p], nbc = pfirst[q - 1] + pnblk[q - 1] - fb0;
-    saux.push_back(make_int4((int)spairs.size(), (int)up.size(), (int)lvp.size(), nbc));
-    lvp.insert(lvp.end(), lpair.begin() + 1, lpair.end());
-    max_nv = std::max(max_nv, nv);
-    for (auto& pr : up) spairs.push_back(make_uchar2((unsigned char)pr.first, (unsigned char)pr.second));
-    sdesc.push_back(make_int4(p, q - p, nv, (int)soff));
-    G.schur_lds = std::max<size_t>(G.schur_lds, sizeof(double) * 6 * (size_t)(q - p) * nv);
-    soff += 36 * up.size() + 6 * nv;
-    schur_poses.push_back(poses);
-    schur_used.push_back(up);
-    schur_used_flag.push_back(upu);
-    p = q;
-  }
-  G.schur_doubles = soff;
-  G.schur_rt_off = 12 * (max_nv - 1);  // the chunks' target poses, then W (schur_chunk)
-  G.schur_lds += sizeof(double) * G.schur_rt_off;
-  G.n_schur = (int)sdesc.size();
-  {  // chunk c's point p → {first GN block, block count} at c · SCHUR_PTS + p (schur_kernel reads it with its descriptor)
-    std::vector<int2> fbt((size_t)G.n_schur * SCHUR_PTS, make_int2(0, 0));
-    for (int c = 0; c < G.n_schur; ++c)
-      for (int q = 0; q < sdesc[c].y; ++q) fbt[(size_t)c * SCHUR_PTS + q] = make_int2(pfirst[sdesc[c].x + q], pnblk[sdesc[c].x + q]);
-    PBA_HIP(G.pt_fb.upload(fbt, e->stream));
-  }
-  // reduced camera system structure: lower blocks (i ≥ j)
-  std::map<std::pair<int, int>, std::vector<int2>> contrib;
-  std::vector<std::vector<int2>> gcon(nf);
-  auto add = [&](int fa, int fb, int o, int flags) {  // contribution block in orientation (fa rows, fb cols)
-    if (fa >= fb) contrib[{fa, fb}].push_back(make_int2(o, flags));
-    else contrib[{fb, fa}].push_back(make_int2(o, flags | C_TRANSPOSE));
-  };
-  std::vector<char> observed(nf, 0);
-  for (int c = 0; c < G.n_chunks; ++c) {
-    const int h = chunk_host[c], o = cdesc[c].w;
-    observed[h] = 1;
-    add(h, h, o, 0);
-    gcon[h].push_back(make_int2(o + 36, 0));
-    for (size_t j = 0; j < chunk_targets[c].size(); ++j) {
-      const int t = chunk_targets[c][j], bo = o + SLOT_LIN_BASE + SLOT_LIN_T * (int)j;
-      observed[t] = 1;
-      add(h, t, bo, 0);
-      add(t, t, bo + 36, 0);
-      gcon[t].push_back(make_int2(bo + 72, 0));
-    }
-  }
-  for (int s = 0; s < G.n_schur; ++s) {
-    const auto& poses = schur_poses[s];
-    const int o = sdesc[s].w;
-    for (size_t u = 0; u < schur_used[s].size(); ++u) {
-      if (!schur_used_flag[s][u]) continue;
-      const int fa = poses[schur_used[s][u].first], fb = poses[schur_used[s][u].second];
-      add(fa, fb, o + 36 * (int)u, C_SCHUR);
-    }
-    for (size_t a = 0; a < poses.size(); ++a)
-      gcon[poses[a]].push_back(make_int2(o + 36 * (int)schur_used[s].size() + 6 * (int)a, C_SCHUR));
-  }
-  // free intrinsics (geometric): two system frames per camera after the keyframes, a dense border (profile from 0)
+  // free intrinsics (geometric): nc cameras in the system
   const int nc = (e->opt_intr && e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC) ? e->n_cams : 0;
-  const int nfs = nf + 2 * nc;
-  G.nc_sys = nc;
-  G.nfs = nfs;
+  const GnPlanInput in{nf, e->n_cams, e->n_pairs, e->n_points, nb,
+                       e->block_point_h.data(), e->block_target_h.data(), e->point_host_h.data(),
+                       e->pair_of_h.data(), e->pair_host_h.data(), e->pair_target_h.data(), e->frame_cam_h.data(),
+                       G.fixed_h.data(), (int)G.fixed_h.size(), G.lpb, G.ppl, G.bpw, nc,
+                       test_hook("PBA_TEST_PBLK_WALK") != nullptr, test_hook("PBA_TEST_ROW_WAVES64") != nullptr,
+                       getenv("PBA_SKYLINE_GLOBAL") != nullptr};
+  GnPlan P;
+  if (int rc = build_gn_plan(in, P)) return rc;
+  G.lin_slots = P.lin_slots;
+  G.n_chunks = P.n_chunks;
+  G.n_gn_points = P.n_gn_points;
+  G.schur_doubles = P.schur_doubles;
+  G.schur_rt_off = P.schur_rt_off;
+  G.schur_lds = P.schur_lds;
+  G.n_schur = P.n_schur;
+  G.nc_sys = in.nc;
+  G.nfs = P.nfs;
   G.dsky_K = -1;  // the multi-GPU summed profile is rebuilt for this problem (ensure_dist_sky)
-  for (int i = 0; i < nfs; ++i) contrib[{i, i}];  // every diagonal block exists
-  std::vector<int> first(nfs), rowp(nfs + 1), last(nfs);
-  for (int i = 0; i < nfs; ++i) first[i] = i < nf ? i : 0;
-  for (auto& kv : contrib) first[kv.first.first] = std::min(first[kv.first.first], kv.first.second);
-  rowp[0] = 0;
-  for (int i = 0; i < nfs; ++i) rowp[i + 1] = rowp[i] + (i - first[i] + 1);
-  G.n_sky = rowp[nfs];
-  G.band = 0;  // over the keyframes (the free-intrinsics border rows start at frame 0)
-  for (int i = 0; i < nf; ++i) G.band = std::max(G.band, i - first[i]);
-  for (int k = 0; k < nfs; ++k) last[k] = k;
-  for (int i = 0; i < nfs; ++i)
-    for (int k = first[i]; k < i; ++k) last[k] = std::max(last[k], i);
-  std::vector<int> ccptr, ccrows;  // the rows of each column's profile, in order
-  profile_columns(first, ccptr, ccrows);
-  if (int rc = build_front_plan(first, rowp, ccptr, ccrows, e->stream, G.front, getenv("PBA_SKYLINE_GLOBAL") == nullptr))
-    return rc;
-  std::vector<int> cptr(G.n_sky + 1, 0), bi(G.n_sky), bj(G.n_sky);
-  std::vector<std::vector<int2>> per(G.n_sky);
-  for (int i = 0; i < nfs; ++i)
-    for (int j = first[i]; j <= i; ++j) {
-      const int s = rowp[i] + (j - first[i]);
-      bi[s] = i;
-      bj[s] = j;
-    }
-  for (auto& kv : contrib) {
-    const int s = rowp[kv.first.first] + (kv.first.second - first[kv.first.first]);
-    per[s] = kv.second;
-  }
-  std::vector<int2> flat;
-  for (int s = 0; s < G.n_sky; ++s) {
-    cptr[s] = (int)flat.size();
-    flat.insert(flat.end(), per[s].begin(), per[s].end());
-  }
-  cptr[G.n_sky] = (int)flat.size();
-  std::vector<int> gptr(nfs + 1);
-  std::vector<int2> gflat;
-  for (int i = 0; i < nfs; ++i) {
-    gptr[i] = (int)gflat.size();
-    if (i < nf) gflat.insert(gflat.end(), gcon[i].begin(), gcon[i].end());
-  }
-  gptr[nfs] = (int)gflat.size();
-  // constant frames: requested + never observed; a camera whose intrinsics no block projects with is constant too
-  std::vector<uint8_t> fixed(nfs, 0);
-  for (int i = 0; i < nf; ++i) fixed[i] = (i < (int)G.fixed_h.size() && G.fixed_h[i]) || !observed[i];
-  if (nc) {
-    // the border's CSR lists: unit pair (camera c, unit u), u < nf keyframe u, u ≥ nf camera u − nf; direct terms from
-    // the blocks whose target camera is c and that touch u (host or target u; u = c: every block of camera c), Schur
-    // terms from the points with a block of camera c that touch u (a block of keyframe u / of camera u − nf)
-    const int nu = nf + nc;
-    std::vector<std::vector<int>> bl((size_t)nc * nu), pl((size_t)nc * nu), pk((size_t)nc * nu);
-    const bool walk = test_hook("PBA_TEST_PBLK_WALK") != nullptr;  // (tests: every target entry walks its point's blocks)
-    std::vector<int> bcam(nb);
-    std::vector<int4> ibrec(nb);
-    std::vector<char> cam_seen(nc, 0);
-    for (int gb = 0; gb < nb; ++gb) {
-      const int b = order[gb], pt = e->block_point_h[b], h = ph[pt], t = e->block_target_h[b], c = e->frame_cam_h[t];
-      bcam[gb] = c;
-      ibrec[gb] = make_int4(b, pt, h, t);
-      cam_seen[c] = 1;
-      bl[(size_t)c * nu + h].push_back((int)((unsigned)gb | 0x80000000u));  // (bit 31: the unit hosts the block)
-      bl[(size_t)c * nu + t].push_back(gb);
-      bl[(size_t)c * nu + nf + c].push_back(gb);
-    }
-    for (int q = 0; q < ngp; ++q) {
-      std::vector<int> cams, units{phost[q]};
-      for (int gb = pfirst[q]; gb < pfirst[q] + pnblk[q]; ++gb) {
-        if (std::find(cams.begin(), cams.end(), bcam[gb]) == cams.end()) cams.push_back(bcam[gb]);
-        if (std::find(units.begin(), units.end(), gtgt[gb]) == units.end()) units.push_back(gtgt[gb]);
-      }
-      for (int c : cams) units.push_back(nf + c);
-      for (int c : cams)
-        for (int u : units) {
-          pl[(size_t)c * nu + u].push_back(q);
-          // the border kernel's Schur term for keyframe u: −1 u hosts the point, else its one block targeting u
-          int by = -1;
-          if (u < nf && u != phost[q]) {
-            int n_u = 0;
-            for (int gb = pfirst[q]; gb < pfirst[q] + pnblk[q]; ++gb)
-              if (gtgt[gb] == u) {
-                by = gb;
-                ++n_u;
-              }
-            if (n_u != 1 || walk) by = -2;
-          }
-          pk[(size_t)c * nu + u].push_back(by);
-        }
-    }
-    std::vector<int> bp(1, 0), bflat, pp(1, 0), pflat, pkflat;
-    for (size_t L = 0; L < bl.size(); ++L) {
-      bflat.insert(bflat.end(), bl[L].begin(), bl[L].end());
-      bp.push_back((int)bflat.size());
-      pflat.insert(pflat.end(), pl[L].begin(), pl[L].end());
-      pkflat.insert(pkflat.end(), pk[L].begin(), pk[L].end());
-      pp.push_back((int)pflat.size());
-    }
-    if (bflat.empty()) bflat.push_back(0);
-    if (pflat.empty()) pflat.push_back(0);
-    if (pkflat.empty()) pkflat.push_back(-1);
-    for (int c = 0; c < nc; ++c) fixed[nf + 2 * c] = fixed[nf + 2 * c + 1] = !cam_seen[c];
-    hipStream_t st0 = e->stream;
-    PBA_HIP(G.ib_rec.upload(ibrec, st0));
-    PBA_HIP(G.ib_cam.upload(bcam, st0));
-    PBA_HIP(G.ib_bptr.upload(bp, st0));
-    PBA_HIP(G.ib_blist.upload(bflat, st0));
-    PBA_HIP(G.ib_pptr.upload(pp, st0));
-    PBA_HIP(G.ib_plist.upload(pflat, st0));
-    PBA_HIP(G.ib_pblk.upload(pkflat, st0));
-    // point-aligned waves for intr_rows_kernel (whole points of ≤ 64 blocks each; a longer point: consecutive waves and
-    // the separate point sums of intr_pw_kernel)
-    {
-      std::vector<int4> wt;
-      bool fits = true;
-      for (int q = 0; q < ngp && fits; ++q) {
-        if (pnblk[q] > 64) fits = false;
-        else if (wt.empty() || wt.back().y + pnblk[q] > 64) wt.push_back(make_int4(pfirst[q], pnblk[q], q, 0));
-        else wt.back().y += pnblk[q];
-      }
-      // (the GN points cover the GN blocks in order: pfirst[q + 1] = pfirst[q] + pnblk[q], checked here)
-      for (int q = 0; q + 1 < ngp && fits; ++q) fits = pfirst[q + 1] == pfirst[q] + pnblk[q];
-      fits = fits && ngp > 0 && pfirst[0] == 0 && pfirst[ngp - 1] + pnblk[ngp - 1] == nb;
-      if (test_hook("PBA_TEST_ROW_WAVES64")) fits = false;  // (tests: the 64-block waves + intr_pw_kernel path)
-      G.ir_waves = fits ? (int)wt.size() : 0;
-      if (fits) PBA_HIP(G.ir_wave.upload(wt, st0));
-    }
-    PBA_HIP(G.ib_data.resize((size_t)nb * kIbStride));
-    PBA_HIP(G.ib_pw.resize((size_t)std::max(ngp, 1) * (8 * nc + 6)));
-    PBA_HIP(G.ib_part.resize((size_t)kCamSplit * (nc * kCamDir + nc * (nc + 1) / 2 * kCamSch)));
-    PBA_HIP(G.intr_new_d.resize((size_t)kCamD * nc));
-    PBA_HIP(G.intr_new_f.resize((size_t)8 * nc));
-    // the candidate records start as the state's (their unprojection half is never read: hosts unproject with the cameras)
-    PBA_HIP(hipMemcpyAsync(G.intr_new_d.p, e->intr_state_d.p, sizeof(double) * kCamD * nc, hipMemcpyDeviceToDevice, st0));
-    PBA_HIP(hipMemcpyAsync(G.intr_new_f.p, e->intr_state.p, sizeof(float) * 8 * nc, hipMemcpyDeviceToDevice, st0));
-  }
-  // upload
+  G.n_sky = P.n_sky;
+  G.n_sky_diag = P.n_sky_diag;
+  G.band = P.band;
+  G.ir_waves = P.ir_waves;
+  const int ngp = P.n_gn_points, nfs = P.nfs;
   hipStream_t st = e->stream;
-  if (e->n_pairs >= (1 << 24)) return fail(PBA_ERR_INVALID_ARGUMENT, "more than 2^24 (host, target) pairs");
-  std::vector<int4> lrec((size_t)G.n_chunks * G.bpw);
-  for (int c = 0; c < G.n_chunks; ++c)
-    for (int s = 0; s < G.bpw; ++s) {
-      const int i = cdesc[c].x + (s < cdesc[c].y ? s : 0), b = order[lpos[i]];
-      lrec[(size_t)c * G.bpw + s] = make_int4(b, e->block_point_h[b], e->pair_of_h[b] | ((int)blt[i] << 24), lpos[i]);
-    }
-  PBA_HIP(G.lin_rec.upload(lrec, st));
-  PBA_HIP(G.chunk_desc.upload(cdesc, st));
+  if (int rc = build_front_plan(P.sky_first, P.sky_row, P.sky_colptr, P.sky_colrows, st, G.front, !in.skyline_global))
+    return rc;
+#define PBA_UP(name) PBA_HIP(upload_plan(G.name, P.name, st))
+  PBA_UP(pt_fb);
+  if (in.nc) {
+    PBA_UP(ib_rec);
+    PBA_UP(ib_cam);
+    PBA_UP(ib_bptr);
+    PBA_UP(ib_blist);
+    PBA_UP(ib_pptr);
+    PBA_UP(ib_plist);
+    PBA_UP(ib_pblk);
+    if (P.ir_waves) PBA_UP(ir_wave);
+    if (int rc = intr_prepare_buffers(e)) return rc;
+  }
+  PBA_UP(lin_rec);
+  PBA_UP(chunk_desc);
   PBA_HIP(G.blk_schur.resize((size_t)nb * kPd));
   PBA_HIP(G.part_lin.resize(std::max<size_t>(G.lin_slots, 1)));
   PBA_HIP(G.blk_schur1.resize((size_t)nb * kPd));  // the device LM loop's second linearisation set
   PBA_HIP(G.pair_rt.resize((size_t)std::max(e->n_pairs, 1) * 12));
   PBA_HIP(G.pair_rt1.resize((size_t)std::max(e->n_pairs, 1) * 12));
   PBA_HIP(G.part_lin1.resize(std::max<size_t>(G.lin_slots, 1)));
-  PBA_HIP(G.pt_first.upload(pfirst, st));
-  PBA_HIP(G.pt_nblk.upload(pnblk, st));
-  PBA_HIP(G.pt_orig.upload(porig, st));
-  PBA_HIP(G.pt_host.upload(phost, st));
-  {
-    std::vector<int4> prec(ngp), ptgt(ngp);
-    for (int q = 0; q < ngp; ++q) {
-      prec[q] = make_int4(pfirst[q], pnblk[q], phost[q], porig[q]);
-      int t4[4] = {0, 0, 0, 0};
-      for (int u = 0; u < 4 && u < pnblk[q]; ++u) t4[u] = gtgt[pfirst[q] + u];
-      ptgt[q] = make_int4(t4[0], t4[1], t4[2], t4[3]);
-    }
-    PBA_HIP(G.pt_rec.upload(prec, st));
-    PBA_HIP(G.pt_tgt.upload(ptgt, st));
-    std::vector<int4> parec(std::max(e->n_pairs, 1), make_int4(0, 0, 0, 0));
-    for (int q = 0; q < e->n_pairs; ++q) {
-      const int h = e->pair_host_h[q], t = e->pair_target_h[q];
-      parec[q] = make_int4(h, t, e->frame_cam_h[h], e->frame_cam_h[t]);
-    }
-    PBA_HIP(G.pair_rec.upload(parec, st));
-  }
-  PBA_HIP(G.gn_target.upload(gtgt, st));
-  PBA_HIP(G.schur_desc.upload(sdesc, st));
-  PBA_HIP(G.schur_aux.upload(saux, st));
-  PBA_HIP(G.schur_pairs.upload(spairs, st));
-  PBA_HIP(G.blk_lv.upload(blv, st));
-  {
-    std::vector<int4> lvp4(sdesc.size(), make_int4(0, 0, 0, 0));
-    for (size_t c = 0; c < sdesc.size(); ++c) {
-      int l4[4] = {0, 0, 0, 0};
-      for (int l = 0; l < 4 && l < sdesc[c].z - 1; ++l) l4[l] = lvp[saux[c].z + l];
-      lvp4[c] = make_int4(l4[0], l4[1], l4[2], l4[3]);
-    }
-    if (lvp4.empty()) lvp4.push_back(make_int4(0, 0, 0, 0));
-    PBA_HIP(G.schur_lvp4.upload(lvp4, st));
-  }
-  if (lvp.empty()) lvp.push_back(0);
-  PBA_HIP(G.schur_lvp.upload(lvp, st));
+  PBA_UP(pt_first);
+  PBA_UP(pt_nblk);
+  PBA_UP(pt_orig);
+  PBA_UP(pt_host);
+  PBA_UP(pt_rec);
+  PBA_UP(pt_tgt);
+  PBA_UP(pair_rec);
+  PBA_UP(gn_target);
+  PBA_UP(schur_desc);
+  PBA_UP(schur_aux);
+  PBA_UP(schur_pairs);
+  PBA_UP(blk_lv);
+  PBA_UP(schur_lvp4);
+  PBA_UP(schur_lvp);
   PBA_HIP(G.part_schur.resize(std::max<size_t>(G.schur_doubles, 1)));
   PBA_HIP(G.pt_data.resize((size_t)ngp * 8));
   PBA_HIP(G.pt_data1.resize((size_t)ngp * 8));
@@ -2754,34 +1797,26 @@ int gn_prepare(pba_engine* e) {
   PBA_HIP(G.ts_part.resize((size_t)kDecideWgs * kTsCount));
   PBA_HIP(G.ts_count.resize(1));
   PBA_HIP(hipMemsetAsync(G.ts_count.p, 0, sizeof(int), st));
-  PBA_HIP(G.sky_first.upload(first, st));
-  PBA_HIP(G.sky_row.upload(rowp, st));
-  PBA_HIP(G.sky_last.upload(last, st));
-  PBA_HIP(G.sky_colptr.upload(ccptr, st));
-  PBA_HIP(G.sky_colrows.upload(ccrows, st));
-  PBA_HIP(G.sky_cptr.upload(cptr, st));
-  PBA_HIP(G.sky_contrib.upload(flat.empty() ? std::vector<int2>{make_int2(0, 0)} : flat, st));
-  PBA_HIP(G.g_cptr.upload(gptr, st));
-  PBA_HIP(G.g_contrib.upload(gflat.empty() ? std::vector<int2>{make_int2(0, 0)} : gflat, st));
-  PBA_HIP(G.sky_blk_i.upload(bi, st));
-  PBA_HIP(G.sky_blk_j.upload(bj, st));
-  {
-    std::vector<int> dg, od;
-    for (int q = 0; q < (int)bi.size(); ++q) (bi[q] == bj[q] ? dg : od).push_back(q);
-    G.n_sky_diag = (int)dg.size();
-    if (dg.empty()) dg.push_back(0);
-    if (od.empty()) od.push_back(0);
-    PBA_HIP(G.sky_diag.upload(dg, st));
-    PBA_HIP(G.sky_off.upload(od, st));
-  }
-  PBA_HIP(G.fixed.upload(fixed, st));
+  PBA_UP(sky_first);
+  PBA_UP(sky_row);
+  PBA_UP(sky_last);
+  PBA_UP(sky_colptr);
+  PBA_UP(sky_colrows);
+  PBA_UP(sky_cptr);
+  PBA_UP(sky_contrib);
+  PBA_UP(g_cptr);
+  PBA_UP(g_contrib);
+  PBA_UP(sky_blk_i);
+  PBA_UP(sky_blk_j);
+  PBA_UP(sky_diag);
+  PBA_UP(sky_off);
+  PBA_UP(fixed);
   PBA_HIP(G.S.resize((size_t)G.n_sky * 36));
   PBA_HIP(G.L.resize((size_t)G.n_sky * 36));
   if (int rc = configure_local_solver(e)) return rc;
-  PBA_HIP(G.observed.upload(std::vector<uint8_t>(observed.begin(), observed.end()), st));
-  std::vector<uint8_t> req(nf, 0);
-  for (int i = 0; i < nf && i < (int)G.fixed_h.size(); ++i) req[i] = G.fixed_h[i];
-  PBA_HIP(G.fixed_req.upload(req, st));
+  PBA_UP(observed);
+  PBA_UP(fixed_req);
+#undef PBA_UP
   PBA_HIP(G.fixed_dist.resize(nfs));
   PBA_HIP(G.g.resize((size_t)nfs * 6));
   PBA_HIP(G.g_dir.resize((size_t)nfs * 6));
@@ -2815,7 +1850,7 @@ int gn_prepare(pba_engine* e) {
   PBA_HIP(hipStreamSynchronize(st));
   G.prepared = true;
   G.pairs_new_fresh = false;
-  G.fixed_eff = fixed;
+  G.fixed_eff = std::move(P.fixed);
   return PBA_OK;
 }
 
@@ -2949,74 +1984,6 @@ void schur_lds_limit(const GnData& G) {
       (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G.schur_lds);
 }
 
-// Free intrinsics: the last trial's accept (lm: the LM record, else none; accept = false: the point elimination's
-// launch has applied it), then the weighted fp64 rows at the state.
-void enqueue_intr_rows(pba_engine* e, const double* lm, bool accept = true) {
-  GnData& G = e->gn;
-  if (lm && accept) intr_accept_kernel<<<1, 256, 0, e->stream>>>(lm, G.intr_new_d.p, G.intr_new_f.p, e->intr_state_d.p,
-                                                       e->intr_state.p, G.nc_sys);
-  IntrRowsArgs ra{G.ib_rec.p, e->poses.p, e->rho.p, e->u_ref.p, e->u_obs.p, e->frame_cam.p, e->intr_d.p,
-                  e->intr_state_d.p, (double)e->opt.huber_width, G.ib_data.p, e->n_blocks, lm ? lm : G.lm_idle.p};
-  int grid = (e->n_blocks + 255) / 256;
-  if (G.ir_waves > 0) {  // point-aligned waves: the points' W sums too (no intr_pw_kernel)
-    ra.wave_tab = G.ir_wave.p;
-    ra.n_waves = G.ir_waves;
-    ra.pw = G.ib_pw.p;
-    ra.nc = G.nc_sys;
-    grid = (G.ir_waves + 3) / 4;
-  }
-  switch (e->opt.camera_model) {
-    case PBA_CAMERA_PINHOLE: intr_rows_kernel<CAM_PINHOLE><<<grid, 256, 0, e->stream>>>(ra); break;
-    case PBA_CAMERA_DOUBLE_SPHERE: intr_rows_kernel<CAM_DS><<<grid, 256, 0, e->stream>>>(ra); break;
-    case PBA_CAMERA_EUCM: intr_rows_kernel<CAM_EUCM><<<grid, 256, 0, e->stream>>>(ra); break;
-    default: intr_rows_kernel<CAM_KB4><<<grid, 256, 0, e->stream>>>(ra); break;
-  }
-}
-
-// The border rows of the reduced system (free intrinsics) into the skyline S — or, X ≠ nullptr, this rank's undamped
-// border into the exchange buffer's border region (X points at it).
-// arrow: the local solve is an arrow (arrow_solve follows with built = true): its level 0 is built in the same launch as
-// the camera blocks.
-void enqueue_border(pba_engine* e, double lambda, const double* lm, double* X, bool arrow = false) {
-  GnData& G = e->gn;
-  const int nf = e->n_frames, nfs = G.nfs;
-  IntrBorderArgs ba{G.ib_data.p, G.ib_rec.p, G.ib_cam.p, G.pt_rec.p, G.pt_data.p, G.ib_bptr.p, G.ib_blist.p,
-                    G.ib_pptr.p, G.ib_plist.p, G.sky_first.p, G.sky_row.p, G.fixed.p, lm ? lm : G.lm_idle.p, G.S.p,
-                    G.g.p, G.g_dir.p, G.Ddiag.p, nf, G.nc_sys, X, (long long)nfs * 36 + EX_TAIL, G.ib_pw.p, G.ib_pblk.p};
-  const int nb = 2 * G.nc_sys + 1;
-  if (G.ir_waves == 0)  // (else intr_rows_kernel has formed them)
-    intr_pw_kernel<<<(8 * G.n_gn_points + 255) / 256, 256, 0, e->stream>>>(ba, G.n_gn_points);
-#ifndef PBA_INTR_KPW_BIG
-#define PBA_INTR_KPW_BIG 2
-#endif
-  bool fused = nf * G.nc_sys < 512;  // one launch (below) while the keyframe part is small, else three
-  if (const char* tb = test_hook("PBA_TEST_BORDER")) {  // (tests: "fused" / "split" whatever the size)
-    if (!std::strcmp(tb, "fused")) fused = true;
-    else if (!std::strcmp(tb, "split")) fused = false;
-  }
-  const int kpw = fused ? 4 : PBA_INTR_KPW_BIG;  // waves per keyframe block (border_keyframes)
-  double* dpart = G.ib_part.p;
-  double* spart = dpart + (size_t)G.nc_sys * kCamSplit * kCamDir;
-  const int nk_x = (nf * kpw + 3) / 4, ncp = G.nc_sys * (G.nc_sys + 1) / 2;
-  if (fused) {
-    const int n_wg = nk_x * G.nc_sys + kCamSplit * (G.nc_sys + ncp);
-    intr_border_all_kernel<<<n_wg, 256, 0, e->stream>>>(ba, lambda, kpw, nk_x, dpart, spart);
-  } else {
-    intr_border_kernel<<<dim3(nk_x, G.nc_sys), 256, 0, e->stream>>>(ba, lambda, kpw);
-    intr_cam_dir_kernel<<<dim3(kCamSplit, G.nc_sys), 256, 0, e->stream>>>(ba, dpart);
-    intr_cam_sch_kernel<<<dim3(kCamSplit, ncp), 256, 0, e->stream>>>(ba, lambda, spart);
-  }
-  const int fin_blocks = (2 * G.nc_sys * nb * 36 + 3) / 4;
-  if (arrow) {
-    const ArrowArgs aa = arrow_args(e, G.S.p, G.sky_first.p, G.sky_row.p, G.fixed.p);
-    const int build_blocks = (int)((arrow_build_threads(G) + 255) / 256);
-    intr_cam_fin_build_kernel<<<fin_blocks + build_blocks, 256, 0, e->stream>>>(ba, lambda, dpart, spart, aa,
-                                                                               G.ar_batches, fin_blocks);
-  } else {
-    intr_cam_fin_kernel<<<fin_blocks, 256, 0, e->stream>>>(ba, lambda, dpart, spart);
-  }
-}
-
 // Schur complement for λ, assembly and reduced-system solve into G.x (enqueued only).
 // lm: the device LM record (λ, buffer set, done flag read on the device; lambda unused) or nullptr.
 // free_sets (the single-GPU LM loop without free intrinsics): the current set's λ-free partials, scaled in the assembly,
@@ -3090,9 +2057,7 @@ void launch_accept(pba_engine* e, const double* lm) {
   const int na = std::max(npd, G.n_gn_points);
   lm_accept_kernel<<<std::min(1024, (na + 255) / 256), 256, 0, e->stream>>>(lm, G.poses_new.p, G.rho_new.p, G.pt_orig.p,
                                                                              e->poses.p, e->rho.p, npd, G.n_gn_points);
-  if (G.nc_sys)
-    intr_accept_kernel<<<1, 256, 0, e->stream>>>(lm, G.intr_new_d.p, G.intr_new_f.p, e->intr_state_d.p, e->intr_state.p,
-                                                 G.nc_sys);
+  if (G.nc_sys) launch_intr_accept(e, lm);
   e->pairs_fresh = false;
 }
 
@@ -3223,16 +2188,11 @@ int ensure_dist_sky(pba_engine* e, int K) {
   GnData& G = e->gn;
   if (G.dsky_K == K) return PBA_OK;
   const int nf = e->n_frames, nfs = G.nfs;
-  std::vector<int> first(nfs), rowp(nfs + 1, 0), ccptr, ccrows;
+  std::vector<int> first(nfs), rowp, last, ccptr, ccrows;
   for (int i = 0; i < nfs; ++i) first[i] = i < nf ? std::max(0, i - K) : 0;
-  for (int i = 0; i < nfs; ++i) rowp[i + 1] = rowp[i] + (i - first[i] + 1);
-  profile_columns(first, ccptr, ccrows);
+  skyline_profile(first, rowp, last, ccptr, ccrows);
   if (int rc = build_front_plan(first, rowp, ccptr, ccrows, e->stream, G.dfront, true)) return rc;
   // (a front beyond LDS — many cameras or a wide band — is solved through global memory, skyline_solve_kernel)
-  std::vector<int> last(nfs);
-  for (int k = 0; k < nfs; ++k) last[k] = k;
-  for (int i = 0; i < nfs; ++i)
-    for (int k = first[i]; k < i; ++k) last[k] = std::max(last[k], i);
   G.n_dsky = rowp[nfs];
   PBA_HIP(G.dS.resize((size_t)G.n_dsky * 36));
   PBA_HIP(G.dL.resize((size_t)G.n_dsky * 36));
@@ -3240,7 +2200,7 @@ int ensure_dist_sky(pba_engine* e, int K) {
   PBA_HIP(G.dsky_first.upload(first, e->stream));
   PBA_HIP(G.dsky_last.upload(last, e->stream));
   PBA_HIP(G.dsky_colptr.upload(ccptr, e->stream));
-  PBA_HIP(G.dsky_colrows.upload(ccrows.empty() ? std::vector<int>{0} : ccrows, e->stream));
+  PBA_HIP(G.dsky_colrows.upload(ccrows, e->stream));  // (never empty: profile_columns)
   G.dsky_K = K;
   return PBA_OK;
 }

@@ -40,7 +40,7 @@ struct ArrowArgs {
   int nf, nc, ldx, n_ent;
 };
 
-// Device code of two units (arrow_build_kernel; intr_cam_fin_build_kernel in pba_gn.hip), hence in the header:
+// Device code of two units (arrow_build_kernel; intr_cam_fin_build_kernel in pba_gn_intr.hip), hence in the header:
 // level 0 of the band (super-rows of 4 keyframes, identity padding past the last keyframe) and the batch's kArrowNB
 // right-hand-side columns: global column 0 = −g_a, 1 + q = column q of B (border frame nf + q/6, component q % 6),
 // B[6f + r][q] = S(border row, keyframe f)[q % 6][r].  Every batch's columns in one launch: batch bt's b at
@@ -98,8 +98,7 @@ long long arrow_build_threads(const GnData& G);
 int arrow_solve(pba_engine* e, const double* S, const int* first, const int* row, const uint8_t* fixed,
                 bool built = false);
 
-// ---- pba_gn_solve_sky.hip ----
-void profile_columns(const std::vector<int>& first, std::vector<int>& ccptr, std::vector<int>& ccrows);
+// ---- pba_gn_solve_sky.hip ----  (the profile vectors: skyline_profile, pba_gn_plan.h)
 int build_front_plan(const std::vector<int>& first, const std::vector<int>& rowp, const std::vector<int>& ccptr,
                      const std::vector<int>& ccrows, hipStream_t st, FrontPlan& P, bool use);
 void launch_band_cholesky(pba_engine* e);  // band_solve's SOLVER_BAND case: band_solve_kernel<G.band_kernel> on G.Sband

@@ -803,21 +803,6 @@ int launch_front(pba_engine* e, FrontPlan& P, const double* S, double* L, int N)
 namespace pba {
 namespace detail {
 
-// The rows of each column's profile: column k → every i > k with first(i) ≤ k, in order (CSR).
-void profile_columns(const std::vector<int>& first, std::vector<int>& ccptr, std::vector<int>& ccrows) {
-  const int n = (int)first.size();
-  std::vector<std::vector<int>> col(n);
-  for (int i = 0; i < n; ++i)
-    for (int k = first[i]; k < i; ++k) col[k].push_back(i);
-  ccptr.assign(n + 1, 0);
-  ccrows.clear();
-  for (int k = 0; k < n; ++k) {
-    ccptr[k + 1] = ccptr[k] + (int)col[k].size();
-    ccrows.insert(ccrows.end(), col[k].begin(), col[k].end());
-  }
-  if (ccrows.empty()) ccrows.push_back(0);
-}
-
 // front_solve_kernel's plan for a skyline profile (first(i), row offsets rowp, column lists): static slots — a row
 // admitted for column k + 1 never takes a slot in use at column k — and the per-column records (see the kernel).
 // P.lds = 0 when the front does not fit (or use = false): the caller then takes skyline_solve_kernel.
