@@ -1,10 +1,12 @@
-// pba_gn.h — what the Gauss-Newton device units share: pba_gn.hip (elimination, assembly, update, LM loops),
-// pba_gn_linearize.hip (the linearisation), pba_gn_intr.hip (free intrinsics; its own interface is pba_gn_intr.h) and
-// pba_gn_solve_cr.hip (v4f64; the solvers' own interface is pba_gn_solve.h).  The layout constants that the host-only
-// symbolic analysis (pba_gn_plan.cpp) shares with them come from pba_gn_plan.h.
+// pba_gn.h — what the Gauss-Newton device units share: pba_gn.hip (elimination, assembly, update), pba_gn_lm.hip (the LM
+// driver; its interface with pba_gn.hip is pba_gn_lm.h), pba_gn_linearize.hip (the linearisation), pba_gn_intr.hip (free
+// intrinsics; its own interface is pba_gn_intr.h) and pba_gn_solve_cr.hip (v4f64; the solvers' own interface is
+// pba_gn_solve.h).  The layout constants that the host-only symbolic analysis (pba_gn_plan.cpp) shares with them come
+// from pba_gn_plan.h, the LM record's fields from pba_gn_lm_record.h (no HIP either).
 // The pipeline of a trial is described in pba_gn.hip.
 #pragma once
 
+#include "pba_gn_lm_record.h"
 #include "pba_gn_plan.h"
 #include "pba_internal.h"
 
@@ -16,19 +18,7 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 constexpr int kPd = 8;            // point data per GN block: [H_ρρ, g_ρ, W_t(6)] (blk_schur)
 // (SLOT_LIN_*, kChunkTargets, SCHUR_PTS, SCHUR_W, C_*: pba_gn_plan.h, shared with the host-only plan unit)
 
-// LM decision record kept on the device by the single-GPU loop (lm_decide_kernel).
-// The trial's outcome, then the trust-region state the next trial runs with (λ = 1/radius, read by the kernels), the
-// done flag (every later kernel of the solve returns at once: 1 function tolerance, 2 consecutive invalid steps,
-// 3 parameter tolerance, 4 gradient tolerance, 5 minimum trust region radius; lm_decide), the index of the
-// linearisation buffer set holding the current state's normal-equation pieces (flipped on acceptance), and Ceres'
-// bookkeeping: the current state's valid blocks, x_norm (−1 until the first accepted step), consecutive invalid steps,
-// and the trial's step and gradient norms.
-enum : int {
-  kLmCost = 0, kLmCostNew = 1, kLmModel = 2, kLmRel = 3, kLmAccept = 4, kLmStatus = 5, kLmConverged = 6,
-  kLmLambda = 7, kLmRadius = 8, kLmFactor = 9, kLmDone = 10, kLmSet = 11, kLmValid = 12, kLmXNorm = 13,
-  kLmInvalid = 14, kLmStepNorm = 15, kLmGradNorm = 16, kLmDesync = 17, kLmFields = 18
-};
-
+// (the LM decision record's fields kLm* and done reasons kDone*: pba_gn_lm_record.h)
 // The kernels always get a record: the device loop's, or — host-driven steps — GnData::lm_idle (not done, set 0, λ NaN
 // = use the kernel's λ argument).  They read it with their first loads, never behind a branch of its own (a gate
 // read before anything else cost the linearisation ~8 µs of serialised scalar round trips).

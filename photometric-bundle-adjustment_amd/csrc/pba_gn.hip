@@ -1,4 +1,7 @@
-// pba_gn.hip — on-device Gauss-Newton / Levenberg-Marquardt for the photometric (and geometric) BA problem.
+// pba_gn.hip — the stages of an on-device Gauss-Newton / Levenberg-Marquardt trial for the photometric (and geometric)
+// BA problem: point elimination, assembly, update, multi-GPU export / import, and the host-driven entry points
+// (pba_gn_step*, pba_gn_linearize, …).  The LM driver that strings them into trials (the loop, the decision kernels,
+// pba_solve*) is pba_gn_lm.hip; pba_gn_lm.h is what the two units share.
 //
 // Replaces the reference's per-iteration CPU work after the cost functors: the Jacobian writer and
 // gradient accumulation (program_evaluator.h:233-257), the Schur eliminator + reduced camera system
@@ -23,58 +26,34 @@
 //                          partial slots (fp64) and 8 doubles of point data per block; linearize_kernel: the
 //                          14-column form (geometric rows, PBA_LIN_LEGACY).  Both in pba_gn_linearize.hip.
 //   schur_free_decide_kernel  the λ-free point elimination of the new linearisation (P/(1 + λ) in the assembly) and,
-//                          in 16 workgroups counted in by an atomic, the fixed-order trial sums and Ceres' decision.
+//                          in 16 workgroups counted in by an atomic, the fixed-order trial sums and Ceres' decision
+//                          (trial_sums, lm_decide: pba_gn_lm.h).
 // Free intrinsics add intr_rows_kernel and the border kernels (intr_border_*) after the elimination: pba_gn_intr.hip,
 // called through pba_gn_intr.h (only AcceptCopy and intr_update_frame, fused into kernels of this unit, are here);
-// several GPUs exchange the per-rank systems (export_band_kernel, import_kernel / import_sky_kernel, dist_* kernels).
+// several GPUs exchange the per-rank systems (export_band_kernel, import_kernel / import_sky_kernel; the dist_* kernels
+// of their decision are pba_gn_lm.hip's).
 // The index structures all of these read — GN order, chunks, slot offsets, skyline profile, contribution and border
 // lists — come from the host-only symbolic analysis build_gn_plan (pba_gn_plan.cpp); gn_prepare uploads them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <cfloat>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
-#include <thread>
 #include <utility>
 #include <vector>
 
 #include "pba_gn.h"
 #include "pba_gn_intr.h"
+#include "pba_gn_lm.h"
 #include "pba_gn_solve.h"
 
 using namespace pba;
 using namespace pba::detail;
 
 namespace {
-
-// kDoneDesync (multi-GPU): the ranks' decisions of the previous trial differed (kLmDesync = 1 + the number of ranks whose
-// record said done then); every rank ends the solve with an error
-enum : int { kDoneFunction = 1, kDoneInvalid = 2, kDoneParameter = 3, kDoneGradient = 4, kDoneRadius = 5, kDoneDesync = 6 };
-
-// A record's decision as a small integer, identical on ranks with identical records: accept, done != 0 and 10 bits of
-// the trust-region state (λ's bits folded) — summed with its square over the ranks in the next trial's scalar all-reduce
-// (N·Σw² = (Σw)² ⇔ every w equal; exact in fp64 for w < 2^12)
-__device__ inline double decision_word(const double* lm) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(lm[kLmLambda]);
-  unsigned h = (unsigned)(b ^ (b >> 20) ^ (b >> 40) ^ (b >> 60));
-  h = (h ^ (h >> 10) ^ (h >> 20)) & 1023u;
-  return (double)((h << 2) | (lm[kLmDone] != 0.0 ? 2u : 0u) | (lm[kLmAccept] != 0.0 ? 1u : 0u));
-}
-// The published copies of the record (host-coherent page-locked memory): a ring of kRecRing slots of kLmFields fields
-// + the trial's sequence number, trial `seq` in slot seq mod kRecRing.  The host enqueues one trial ahead of the record
-// it waits for, so two records can be in flight; with a single slot, a host thread descheduled for longer than a trial
-// (~0.23 ms at C4) would find the next trial's record over the one it waits for and fail the solve.
-#ifndef PBA_REC_RING
-#define PBA_REC_RING 4
-#endif
-constexpr int kRecRing = PBA_REC_RING, kRecStride = kLmFields + 1;  // (-DPBA_REC_RING=1: the one-slot record, tests)
-__host__ __device__ inline long long rec_slot(double seq) { return ((long long)seq % kRecRing) * kRecStride; }
 
 struct SchurArgs {
   const int4* desc;       // first GN point, n points, n local poses, partial offset (doubles)
@@ -90,12 +69,12 @@ struct SchurArgs {
   const double* lm;       // LM record (λ, set; the loop's or GnData::lm_idle)
   // device LM loop: the previous trial's accept (state ← candidate when the record says accepted), done here by the
   // workgroups before their chunks instead of by a launch of its own; poses == nullptr: nothing to apply
-  double* poses;
-  const double* poses_new;
-  double* rho;
-  const double* rho_new;
-  const int* pt_orig;
-  int n_pose_d, n_gn_points;
+  double* poses = nullptr;
+  const double* poses_new = nullptr;
+  double* rho = nullptr;
+  const double* rho_new = nullptr;
+  const int* pt_orig = nullptr;
+  int n_pose_d = 0, n_gn_points = 0;
   const double* pair_rt;   // per pair [R_th, t_th] of the linearisation in blk_schur / blk_schur1 (W_h = −W_t·Ad)
   const double* pair_rt1;
   const int4* lvp4;        // per chunk: the pairs of local targets 1 … 4
@@ -447,6 +426,8 @@ struct AsmArgs {
   double* g;
   double* g_dir;
   double* Ddiag;
+  // (the fields above and n_sky: asm_args; the rest, zero there, by name where they are used — assemble_kernel's in
+  // enqueue_solve, export_band_kernel's in enqueue_export)
   double* Sband;   // optional dense band copy (block c of row i = column i − B + c), B = band
   int band;
   int n_sky;
@@ -1181,245 +1162,6 @@ __global__ __launch_bounds__(kBlockThreads) void cost_reduce_kernel(const float*
   wg_reduce2(c, v, red + 2 * blockIdx.x);
 }
 
-// The LM trial's decision on the device (trust_region_minimizer.cc semantics, the same sums and order as the host
-// code of the distributed loop): model decrease from the update partials (slots [0, gp + gq)), candidate cost from
-// the cost partials (slots [gp + gq, gp + gq + gc)), accepted when the solve succeeded, the model predicts a
-// decrease and (cost − cost_new) / model > min_relative_decrease.  On acceptance the record's current cost becomes
-// the candidate's.  One workgroup: strided per-thread sums, then a fixed-order tree in LDS (deterministic).
-// The record is also published to page-locked, host-coherent memory (host_rec: the kLmFields values, then the trial's
-// sequence number after a system-scope fence), so the host learns the decision by polling instead of through a copy
-// and a stream event (each of which left the GPU idle ~6 µs).
-constexpr int kDecideThreads = 1024;
-
-// Ceres' termination options of the LM loop (solver.h:278-322; pba_solver_options)
-struct DecideOpts {
-  double min_rel, ftol, ptol, gtol, max_radius, min_radius;
-  int max_invalid;
-};
-
-// The trial's sums: the pose part (identical on every rank of a distributed solve: same summed system, same step) and
-// the point part with the candidate's cost and valid blocks (summed over the ranks).
-enum : int {
-  kTsPoseG = 0, kTsPoseD, kTsPoseStep2, kTsPoseXNorm2, kTsPoseGMax,
-  kTsPtG, kTsPtD, kTsCost, kTsValid, kTsPtStep2, kTsPtXNorm2, kTsPtGMax, kTsCount
-};
-
-// The trial's decision (one lane): trust_region_minimizer.cc:85-133 + levenberg_marquardt_strategy.cc:146-160 over the
-// summed trial quantities t[kTs*] and the record lm.  In Ceres' order:
-//   gradient tolerance at the current state (FinalizeIteration… :336-355, GradientToleranceReached :668-684): checked
-//     here, before the step, because this trial is the first to see the current state's gradient; the trial is void
-//     (done 4, not an iteration);
-//   invalid step — solver failure or no predicted decrease (:400-439) — HandleInvalidStep (:453-484): the 5th
-//     consecutive one ends the solve with FAILURE (done 2, not an iteration), earlier ones shrink the radius;
-//   candidate cost: infinite (DBL_MAX, :771-778) when a block valid at the current state is invalid at the candidate;
-//   parameter tolerance (:706-726, step_norm ≤ ptol (x_norm + ptol) with x_norm = −1 until the first accepted step,
-//     :185 / :814) → done 3;  function tolerance (:729-748) → done 1 (neither step applied);
-//   IsStepSuccessful (:781-803) → accept (radius = min(max_radius, radius / max(1/3, 1 − (2ρ − 1)³)), :146-153) or
-//     reject (radius /= factor, factor *= 2, :155-160);  MinTrustRegionRadiusReached (:687-703) → done 5.
-__device__ void lm_decide(const double* t, int st, const DecideOpts& o, double* lm) {
-  const double lambda = lm[kLmLambda];
-  const double model = __dadd_rn(__dmul_rn(0.5, __dsub_rn(__dmul_rn(lambda, t[kTsPoseD]), t[kTsPoseG])),
-                                 __dmul_rn(0.5, __dsub_rn(__dmul_rn(lambda, t[kTsPtD]), t[kTsPtG])));
-  const double cost = lm[kLmCost];
-  const double gnorm = fmax(t[kTsPoseGMax], t[kTsPtGMax]);
-  double radius = lm[kLmRadius], factor = lm[kLmFactor], done = 0.0, invalid = lm[kLmInvalid];
-  bool accept = false, converged = false;
-  const bool valid_step = st == 0 && model > 0.0;
-  const double c = t[kTsValid] < lm[kLmValid] ? DBL_MAX : t[kTsCost];
-  const double step = sqrt(t[kTsPoseStep2] + t[kTsPtStep2]);
-  const double rel = (cost - c) / model;
-  if (gnorm <= o.gtol) {
-    done = 4.0;
-  } else if (!valid_step) {
-    invalid += 1.0;
-    if (invalid >= (double)o.max_invalid) {
-      done = 2.0;
-    } else {
-      radius /= factor;  // StepIsInvalid = StepRejected(0)
-      factor *= 2.0;
-      if (radius <= o.min_radius) done = 5.0;
-    }
-  } else {
-    invalid = 0.0;
-    if (step <= o.ptol * (lm[kLmXNorm] + o.ptol)) {
-      done = 3.0;
-      converged = true;
-    } else if (fabs(cost - c) <= o.ftol * cost) {
-      done = 1.0;
-      converged = true;
-    } else if (rel > o.min_rel) {
-      accept = true;
-      const double q = 2.0 * rel - 1.0;
-      radius = fmin(o.max_radius, radius / fmax(1.0 / 3.0, 1.0 - q * q * q));
-      factor = 2.0;
-    } else {
-      radius /= factor;
-      factor *= 2.0;
-      if (radius <= o.min_radius) done = 5.0;
-    }
-  }
-  lm[kLmConverged] = converged ? 1.0 : 0.0;
-  lm[kLmCostNew] = c;
-  lm[kLmModel] = model;
-  lm[kLmRel] = rel;
-  lm[kLmAccept] = accept ? 1.0 : 0.0;
-  lm[kLmStatus] = (double)st;
-  lm[kLmStepNorm] = step;
-  lm[kLmGradNorm] = gnorm;
-  if (accept) {
-    lm[kLmCost] = c;
-    lm[kLmValid] = t[kTsValid];
-    lm[kLmXNorm] = sqrt(t[kTsPoseXNorm2] + t[kTsPtXNorm2]);
-    lm[kLmSet] = 1.0 - lm[kLmSet];  // the candidate's linearisation (the spare set) is now the current one
-  }
-  lm[kLmInvalid] = invalid;
-  lm[kLmRadius] = radius;
-  lm[kLmFactor] = factor;
-  lm[kLmLambda] = 1.0 / radius;
-  lm[kLmDone] = done;
-}
-
-// The trial's sums from the update and cost partials (one workgroup; deterministic).  Slots: red [0, gp) poses,
-// [gp, gp + gq) points (model decrease parts), [gp + gq, gp + gq + gc) the candidate's (cost, valid) — one slot per
-// linearisation chunk, 12.5k at C4; red2 / gmax [0, gp + gq) (update_kernel).  The red2 / gmax slots one per
-// thread, then one strided pass over red with U slots per thread in flight, then xor butterflies per wave and the
-// waves in order (U loads of three arrays spilled 172 B per lane at 1024 threads: 16 µs per decision).  t: the
-// totals, in LDS.
-// lo, hi: only the slots [lo, hi) of both passes (a slice of the sums, schur_free_decide_kernel's decision workgroups).
-template <int N>
-__device__ void trial_sums(const double* __restrict__ red, const double* __restrict__ red2,
-                           const double* __restrict__ gmax, int gp, int gq, int gc, double* t, int lo = 0,
-                           int hi = 0x7fffffff) {
-  constexpr int U = 8;
-  __shared__ double part[kTsCount][N / 64];
-  double v[kTsCount] = {};
-  const int S0 = gp + gq, S = min(S0, hi), E = min(S0 + gc, hi);
-  const double2* r1 = reinterpret_cast<const double2*>(red);
-  const double2* r2 = reinterpret_cast<const double2*>(red2);
-  // the update slots' norms and gradient maxima: one slot per thread, loaded before the red pass so that both are
-  // in flight together (S ≤ N unless the problem has > 260k points: a tail loop then)
-  const int i_s = lo + (int)threadIdx.x;
-  const double2 ys = i_s < S ? r2[i_s] : make_double2(0.0, 0.0);
-  const double ms = i_s < S ? gmax[i_s] : 0.0;
-  for (int i0 = lo + (int)threadIdx.x; i0 < E; i0 += U * N) {
-    double2 x[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = i0 + u * N;
-      x[u] = i < E ? r1[i] : make_double2(0.0, 0.0);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {  // selects, not a computed index (that put v in scratch memory)
-      const int i = i0 + u * N;
-      const bool p = i < gp, t = i >= gp && i < S0;
-      v[kTsPoseG] += p ? x[u].x : 0.0;
-      v[kTsPoseD] += p ? x[u].y : 0.0;
-      v[kTsPtG] += t ? x[u].x : 0.0;
-      v[kTsPtD] += t ? x[u].y : 0.0;
-      v[kTsCost] += i >= S0 ? x[u].x : 0.0;  // (slots past E loaded as zeros)
-      v[kTsValid] += i >= S0 ? x[u].y : 0.0;
-    }
-  }
-  auto add_small = [&](int i, const double2& y, double m) {
-    if (i < gp) {
-      v[kTsPoseStep2] += y.x;
-      v[kTsPoseXNorm2] += y.y;
-      v[kTsPoseGMax] = fmax(v[kTsPoseGMax], m);
-    } else if (i < S) {
-      v[kTsPtStep2] += y.x;
-      v[kTsPtXNorm2] += y.y;
-      v[kTsPtGMax] = fmax(v[kTsPtGMax], m);
-    }
-  };
-  add_small(i_s, ys, ms);
-  for (int i = i_s + N; i < S; i += N) add_small(i, r2[i], gmax[i]);
-  auto is_max = [](int q) { return q == kTsPoseGMax || q == kTsPtGMax; };
-  // a wave past the update slots holds only candidate-cost sums: its other ten are zeros, not butterflied (the same
-  // totals: only zeros are left out)
-  const bool upd = __builtin_amdgcn_readfirstlane(lo + ((int)threadIdx.x & ~63)) < S;
-#pragma unroll
-  for (int q = 0; q < kTsCount; ++q) {
-    if (!upd && q != kTsCost && q != kTsValid) continue;
-    for (int m = 32; m >= 1; m >>= 1) {
-      const double o = __shfl_xor(v[q], m, 64);
-      v[q] = is_max(q) ? fmax(v[q], o) : v[q] + o;
-    }
-  }
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < kTsCount; ++q) part[q][threadIdx.x >> 6] = v[q];
-  __syncthreads();
-  // the waves in order, one thread per sum (one thread summing all twelve, 192 dependent LDS reads, was ~8 µs)
-  if (threadIdx.x < kTsCount) {
-    const int q = threadIdx.x;
-    double w16[N / 64];
-#pragma unroll
-    for (int w = 0; w < N / 64; ++w) w16[w] = part[q][w];
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < N / 64; ++w) s = is_max(q) ? fmax(s, w16[w]) : s + w16[w];
-    t[q] = s;
-  }
-  __syncthreads();
-}
-
-// Publish the record to page-locked, host-coherent memory (wave 0): lane i stores field i, every store completes, then
-// lane 0 stores the sequence number the host polls for with a system-scope release.
-// Every store is a system-scope relaxed atomic (`sc0 sc1`: written through to memory, whatever the page's cache
-// policy), and the sequence number is stored only after every field store has completed (vmcnt(0)).  A release fence
-// at system scope instead (`buffer_wbl2`) wrote back every dirty line the candidate linearisation had left in L2: the
-// decision launch took 14.5-16.4 µs against 8.6 µs (profiles/r3_gn_trial_trace_*).
-__device__ void publish_record(const double* s_rec, double* host_rec, double seq) {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int l = threadIdx.x;
-  if (l < kLmFields) __hip_atomic_store(host_rec + l, s_rec[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every lane's field store has completed
-  __builtin_amdgcn_wave_barrier();
-  if (l == 0) __hip_atomic_store(host_rec + kLmFields, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__global__ __launch_bounds__(kDecideThreads) void lm_decide_kernel(const double* __restrict__ red,
-                                                                   const double* __restrict__ red2,
-                                                                   const double* __restrict__ gmax, int gp, int gq,
-                                                                   int gc, const int* __restrict__ status,
-                                                                   const DecideOpts o, double* __restrict__ lm,
-                                                                   double* __restrict__ host_rec, double seq) {
-  // a trial enqueued ahead of the one that ended the solve returns — tested after the sums, so the record's load is in
-  // flight with the partials' instead of a round trip of its own before them (the partials are always readable)
-  const double done = lm[kLmDone];
-  __shared__ double t[kTsCount];
-  trial_sums<kDecideThreads>(red, red2, gmax, gp, gq, gc, t);
-  if (done != 0.0 || threadIdx.x >= 64) return;  // wave 0 publishes; lane 0 decides
-  __shared__ double s_rec[kLmFields];
-  if (threadIdx.x == 0) {
-    lm_decide(t, *status, o, lm);
-    for (int i = 0; i < kLmFields; ++i) s_rec[i] = lm[i];
-  }
-  if (host_rec) publish_record(s_rec, host_rec, seq);
-}
-
-// The LM record of a new solve, on the device: the initial cost and valid blocks summed from the initial linearisation's
-// chunk partials (slots [0, gc) of red — the same partials, in the same order, as a trial's candidate cost), the trust
-// region, nothing done, buffer set 0, x_norm −1.  The host enqueues the first trials behind it instead of reading the cost
-// back first (a host round trip with the GPU idle, once per solve); init[0..1] = the initial cost and valid blocks.
-__global__ __launch_bounds__(kDecideThreads) void lm_init_kernel(const double* __restrict__ red, int gc, double radius,
-                                                                 double* __restrict__ lm, double* __restrict__ init) {
-  __shared__ double t[kTsCount];
-  trial_sums<kDecideThreads>(red, red, red, 0, 0, gc, t);
-  if (threadIdx.x != 0) return;
-  for (int i = 0; i < kLmFields; ++i) lm[i] = 0.0;
-  lm[kLmCost] = t[kTsCost];
-  lm[kLmValid] = t[kTsValid];
-  lm[kLmXNorm] = -1.0;
-  lm[kLmRadius] = radius;
-  lm[kLmFactor] = 2.0;
-  lm[kLmLambda] = 1.0 / radius;
-  init[0] = t[kTsCost];
-  init[1] = t[kTsValid];
-}
-
 // ---- the single-GPU LM loop's λ-free point elimination ---------------------------------------------------------------
 // For a point whose H_ρρ lies inside the LM diagonal's clamp [1e-6, 1e32] (levenberg_marquardt_strategy.cc), the damped
 // H' = H + λ·clamp(H) = (1 + λ)·H, so its Schur terms W Wᵀ / H' and W g / H' are (1 + λ)⁻¹ times the λ-free W Wᵀ / H and
@@ -1433,26 +1175,7 @@ __global__ __launch_bounds__(kDecideThreads) void lm_init_kernel(const double* _
 // form the λ-free partials and point data of the set linearize_kernel has just written (lin_set); the two parts share no
 // data, so the decision costs no launch and runs beside the elimination.  The elimination never reads the record's set
 // (the decision may flip it meanwhile); only its done flag (a workgroup that sees the solve ended skips its chunk: nothing
-// reads it then).
-struct DecideArgs {
-  const double* red;
-  const double* red2;
-  const double* gmax;
-  int gp, gq, gc;
-  const int* status;
-  DecideOpts o;
-  double* lm;
-  double* host_rec;   // the published record slot, or nullptr
-  double seq;
-  int init;           // 1: a new solve's record (lm_init_kernel), 0: the trial's decision
-  double radius;      // init: the initial trust-region radius
-  double* init_out;   // init: [initial cost, valid blocks]
-  double* ts_part;    // [kDecideWgs][kTsCount]: the decision workgroups' slices of the sums
-  int* ts_count;      // their arrivals (0 between launches)
-};
-// Workgroups of schur_free_decide_kernel that sum the trial's partial slots, a slice each: one workgroup alone took ~20 µs
-// for the 13.5k slots at C4 (seven dependent memory rounds), longer than the elimination beside it.
-constexpr int kDecideWgs = 16;
+// reads it then).  (DecideArgs, kDecideWgs and the decision's device code: pba_gn_lm.h.)
 struct FreeSets {
   double* part[2];    // λ-free Schur partials per linearisation set
   double* pt[2];      // point data per set ([H, g, W_h(6)] per GN point, undamped)
@@ -1579,105 +1302,6 @@ __global__ __launch_bounds__(kBlockThreads) void schur_gate_kernel(const SchurAr
   ac.store(g);
 }
 
-// Multi-GPU trial, before the scalar all-reduce: this rank's sums, written to the exchange buffer's kExScalars scalar
-// slots Y for the Σ over ranks:
-//   Y[0..7]  the point part: [δρ·g, δρ·D·δρ, candidate cost, candidate valid blocks, Σδρ², Σρ_new², points above the
-//            gradient tolerance, 0] (the gradient test needs only whether some rank's point gradient exceeds the
-//            tolerance: a count sums exactly);
-//   Y[8..14] the pose part [g·δ, δ·D·δ, Σδ², Σx_new², max|g|] and the reduced solve's status, from rank 0 only (0 on the
-//            other ranks).  Every rank computes them from the same summed system with the same kernels, so they agree
-//            bit for bit anyway; summing rank 0's copy makes the decision inputs identical on every rank by construction
-//            (a decision that differed between ranks would leave their collective sequences mismatched: a hang).
-// rank0 = −1 (a host-callback collective, which does not know the ranks): Y[8..14] stay 0 and the decision reads the
-// rank's own pose part from tpose.  tpose: [pose part (5) | this rank's point gradient max-norm | solve status].
-constexpr int kExScalars = 16;
-__global__ __launch_bounds__(kDecideThreads) void dist_sums_kernel(const double* __restrict__ red,
-                                                                   const double* __restrict__ red2,
-                                                                   const double* __restrict__ gmax, int gp, int gq, int gc,
-                                                                   double gtol, const double* __restrict__ lm,
-                                                                   const int* __restrict__ status, int rank0,
-                                                                   double* __restrict__ tpose, double* __restrict__ Y) {
-  const double done = lm[kLmDone];  // (tested after the sums, as lm_decide_kernel)
-  __shared__ double t[kTsCount];
-  trial_sums<kDecideThreads>(red, red2, gmax, gp, gq, gc, t);
-  if (threadIdx.x != 0) return;
-  // the previous decision's word, with its square, and whether it ended the solve on this rank: every rank, done or not
-  const double w = decision_word(lm);
-  Y[7] = done != 0.0 ? 1.0 : 0.0;
-  Y[14] = w;
-  Y[15] = w * w;
-  if (done != 0.0) {  // (the sums are not used; zeros keep them finite)
-    for (int q = 0; q < 7; ++q) Y[q] = 0.0;
-    for (int q = 8; q < 14; ++q) Y[q] = 0.0;
-    return;
-  }
-  for (int q = 0; q < 5; ++q) tpose[q] = t[kTsPoseG + q];
-  tpose[5] = t[kTsPtGMax];
-  tpose[6] = (double)*status;
-  Y[0] = t[kTsPtG];
-  Y[1] = t[kTsPtD];
-  Y[2] = t[kTsCost];
-  Y[3] = t[kTsValid];
-  Y[4] = t[kTsPtStep2];
-  Y[5] = t[kTsPtXNorm2];
-  Y[6] = t[kTsPtGMax] > gtol ? 1.0 : 0.0;
-  for (int q = 0; q < 5; ++q) Y[8 + q] = rank0 == 1 ? t[kTsPoseG + q] : 0.0;
-  Y[13] = rank0 == 1 ? (double)*status : 0.0;
-}
-
-// Multi-GPU decision from the summed Y: the same lm_decide on every rank (identical inputs), so every rank takes the
-// same decision; the reported gradient norm is this rank's view (the pose part and its own points).  First the check of
-// the previous decision (decision_word over the ranks, n_ranks of them): if the ranks' records differed, every rank
-// ends the solve here (done = kDoneDesync, kLmDesync = 1 + the number of ranks that had stopped) — the host loops then
-// match their remaining collectives (lm_loop) and report the error instead of hanging.  The record is published even
-// when the solve was already done, so a host that stopped can read this check.  perturb_seq (tests,
-// PBA_TEST_PERTURB_DECISION): this rank's decision of that trial is overridden (mode 1 flips accept, 2 ends the solve).
-__global__ __launch_bounds__(64) void dist_decide_kernel(const double* __restrict__ Y, const double* __restrict__ tpose,
-                                                         int local, const DecideOpts o, double* __restrict__ lm,
-                                                         double* __restrict__ host_rec, double seq, int n_ranks,
-                                                         double perturb_seq, int perturb_mode, int verify_only) {
-  __shared__ double s_rec[kLmFields];
-  if (threadIdx.x == 0) {
-    const bool desync = (double)n_ranks * Y[15] != Y[14] * Y[14];
-    if (desync) {
-      lm[kLmDone] = kDoneDesync;
-      lm[kLmDesync] = Y[7] + 1.0;
-      lm[kLmAccept] = 0.0;
-    } else if (lm[kLmDone] == 0.0 && !verify_only) {
-      const double* pose = local ? tpose : Y + 8;  // [pose part (5) | …, status at 6 resp. 5]
-      double t[kTsCount];
-      for (int q = 0; q < 5; ++q) t[kTsPoseG + q] = pose[q];
-      t[kTsPtG] = Y[0];
-      t[kTsPtD] = Y[1];
-      t[kTsCost] = Y[2];
-      t[kTsValid] = Y[3];
-      t[kTsPtStep2] = Y[4];
-      t[kTsPtXNorm2] = Y[5];
-      // no rank's point gradient above the tolerance: the test then depends on the pose part alone (identical)
-      t[kTsPtGMax] = Y[6] > 0.0 ? INFINITY : 0.0;
-      lm_decide(t, (int)(local ? tpose[6] : Y[13]), o, lm);
-      lm[kLmGradNorm] = fmax(pose[4], tpose[5]);
-      if (seq == perturb_seq) {
-        if (perturb_mode == 1) lm[kLmAccept] = 1.0 - lm[kLmAccept];
-        else lm[kLmDone] = kDoneFunction;
-      }
-    }
-    for (int i = 0; i < kLmFields; ++i) s_rec[i] = lm[i];
-  }
-  if (host_rec) publish_record(s_rec, host_rec, seq);
-}
-
-// The check of the last decision of a multi-GPU solve (no trial follows it): the decision word into Y as dist_sums_kernel
-// writes it, every other slot zero.
-__global__ void dist_verify_kernel(const double* __restrict__ lm, double* __restrict__ Y) {
-  if (threadIdx.x != 0) return;
-  const double w = decision_word(lm);
-  for (int q = 0; q < kExScalars; ++q) Y[q] = 0.0;
-  Y[7] = lm[kLmDone] != 0.0 ? 1.0 : 0.0;
-  Y[14] = w;
-  Y[15] = w * w;
-}
-
 // The accepted candidate becomes the state (device-side accept, gated by the decision record; lm == nullptr: always).
 // Only the points of the Gauss-Newton problem are copied (through pt_orig): rho_new holds nothing for a point with
 // no residual block, and such a point keeps its state, as a parameter Ceres never sees would.
@@ -1695,19 +1319,24 @@ __global__ void lm_accept_kernel(const double* __restrict__ lm, const double* __
   }
 }
 
+}  // namespace
+
 // ------------------------------------------------------------------------------------------------
-// host side
+// host side: the stages the LM driver calls (declared in pba_gn_lm.h), and — static — what only this unit uses
 // ------------------------------------------------------------------------------------------------
-int gn_lpb(const pba_engine* e) { return e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC ? 4 : 8; }
+namespace pba {
+namespace detail {
+
+static int gn_lpb(const pba_engine* e) { return e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC ? 4 : 8; }
 // rows per lane of the linearisation: 1 up to 8 px (one lane per row), ⌈P/8⌉ above (linearize_adj_kernel<·, PPL>)
-int gn_ppl(const pba_engine* e) { return e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC ? 1 : (e->P + 7) / 8; }
+static int gn_ppl(const pba_engine* e) { return e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC ? 1 : (e->P + 7) / 8; }
 
 // A plan vector (pba_gn_plan.h) into its device buffer: the plan's records are the device's int4 / int2 / uchar2 byte
 // for byte.
 static_assert(sizeof(PlanInt4) == sizeof(int4) && sizeof(PlanInt2) == sizeof(int2) && sizeof(PlanUchar2) == sizeof(uchar2),
               "the plan's records are uploaded as the device's vector types");
 template <class D, class H>
-hipError_t upload_plan(DevBuf<D>& buf, const std::vector<H>& h, hipStream_t s) {
+static hipError_t upload_plan(DevBuf<D>& buf, const std::vector<H>& h, hipStream_t s) {
   static_assert(sizeof(D) == sizeof(H), "element for element");
   const hipError_t rc = buf.resize(h.size());
   if (rc != hipSuccess || h.empty()) return rc;
@@ -1716,7 +1345,7 @@ hipError_t upload_plan(DevBuf<D>& buf, const std::vector<H>& h, hipStream_t s) {
 
 // The symbolic analysis (build_gn_plan: GN block order, chunks, slot layouts, skyline profile, contribution and border
 // lists) into GnData, in upload order, and the buffers sized by it.
-int gn_prepare(pba_engine* e) {
+static int gn_prepare(pba_engine* e) {
   GnData& G = e->gn;
   const int nb = e->n_blocks, nf = e->n_frames;
   if (nb <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_blocks first");
@@ -1871,7 +1500,7 @@ int ensure_prepared(pba_engine* e) {
 }
 
 // Σ of 2-vectors over `slots` reduction slots, in fixed order on the host.
-int read_red(pba_engine* e, int slots, double* a, double* b) {
+static int read_red(pba_engine* e, int slots, double* a, double* b) {
   GnData& G = e->gn;
   PBA_HIP(hipMemcpyAsync(G.red_h.data(), G.red.p, sizeof(double) * 2 * slots, hipMemcpyDeviceToHost, e->stream));
   PBA_HIP(hipStreamSynchronize(e->stream));
@@ -1885,7 +1514,7 @@ int read_red(pba_engine* e, int slots, double* a, double* b) {
   return PBA_OK;
 }
 
-int total_cost(pba_engine* e, double* cost, int* n_valid) {
+static int total_cost(pba_engine* e, double* cost, int* n_valid) {
   const int grid = std::min(1024, (e->n_blocks + kBlockThreads - 1) / kBlockThreads);
   cost_reduce_kernel<<<grid, kBlockThreads, 0, e->stream>>>(e->cost.p, e->valid.p, e->n_blocks, e->gn.red.p);
   PBA_HIP(hipGetLastError());
@@ -1901,9 +1530,8 @@ int total_cost(pba_engine* e, double* cost, int* n_valid) {
 // the candidate's, and wg_red the slots of the per-chunk cost partials the decision sums.
 // cand_intr: with free intrinsics, project with the candidate's (G.intr_new_*) instead of the state's.
 // mark_set: record the set written (and clear its degen flag) for the λ-free elimination that follows.
-int linearize(pba_engine* e, double* cost, const double* lm = nullptr, const PairRec* pairs = nullptr,
-              const double* rho = nullptr, double* wg_red = nullptr, int* n_valid = nullptr, bool cand_intr = false,
-              bool mark_set = false) {
+int linearize(pba_engine* e, double* cost, const double* lm, const PairRec* pairs, const double* rho, double* wg_red,
+              int* n_valid, bool cand_intr, bool mark_set) {
   GnData& G = e->gn;
   if (!pairs) {
     launch_pairs(e, e->poses.p, e->pairs.p);
@@ -1929,8 +1557,8 @@ int linearize(pba_engine* e, double* cost, const double* lm = nullptr, const Pai
 // L(0) − L(δ) = −gᵀδ − ½δᵀHδ = ½(λ δᵀDδ − gᵀδ)  (since (H + λD)δ = −g): pose part and point part.
 // Candidate poses/points and the model-decrease partials into reduction slots [0, gp + gq) of G.red.
 // free_sets: the single-GPU LM loop's per-set point data (the record says which set is current), else G.pt_data.
-void enqueue_updates(pba_engine* e, double lambda, const uint8_t* fixed, int* gp_out, int* gq_out,
-                     const double* lm = nullptr, bool free_sets = false) {
+void enqueue_updates(pba_engine* e, double lambda, const uint8_t* fixed, int* gp_out, int* gq_out, const double* lm,
+                     bool free_sets) {
   GnData& G = e->gn;
   const int nf = e->n_frames, nfs = G.nc_sys ? G.nfs : nf;
   const int gp = (nfs + kBlockThreads - 1) / kBlockThreads;
@@ -1950,7 +1578,7 @@ void enqueue_updates(pba_engine* e, double lambda, const uint8_t* fixed, int* gp
   *gq_out = gq;
 }
 
-void model_from_slots(const GnData& G, double lambda, int gp, int gq, double* model_pose, double* model_points) {
+static void model_from_slots(const GnData& G, double lambda, int gp, int gq, double* model_pose, double* model_points) {
   double dg = 0, dD = 0, qg = 0, qD = 0;
   for (int i = 0; i < gp; ++i) { dg += G.red_h[2 * i]; dD += G.red_h[2 * i + 1]; }
   for (int i = gp; i < gp + gq; ++i) { qg += G.red_h[2 * i]; qD += G.red_h[2 * i + 1]; }
@@ -1958,8 +1586,8 @@ void model_from_slots(const GnData& G, double lambda, int gp, int gq, double* mo
   *model_points = 0.5 * (lambda * qD - qg);
 }
 
-int finish_step(pba_engine* e, double lambda, const uint8_t* fixed, double* model_pose, double* model_points,
-                int* solver_status) {
+static int finish_step(pba_engine* e, double lambda, const uint8_t* fixed, double* model_pose,
+                       double* model_points, int* solver_status) {
   GnData& G = e->gn;
   int status = 0;
   PBA_HIP(hipMemcpyAsync(&status, G.status.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -1976,8 +1604,66 @@ int finish_step(pba_engine* e, double lambda, const uint8_t* fixed, double* mode
   return PBA_OK;
 }
 
+// The elimination kernels' arguments that every launch shares — the chunk tables, both linearisation sets, the outputs —
+// with the record lm; no accept (poses == nullptr) and no intrinsics copy: a launch that applies them sets them by name.
+static SchurArgs schur_args(const pba_engine* e, const double* lm) {
+  const GnData& G = e->gn;
+  SchurArgs sa{};
+  sa.desc = G.schur_desc.p;
+  sa.aux = G.schur_aux.p;
+  sa.pairs = G.schur_pairs.p;
+  sa.pt_fb = G.pt_fb.p;
+  sa.blk_lv = G.blk_lv.p;
+  sa.blk_schur = G.blk_schur.p;
+  sa.blk_schur1 = G.blk_schur1.p;
+  sa.part_schur = G.part_schur.p;
+  sa.pt_data = G.pt_data.p;
+  sa.n_chunks = G.n_schur;
+  sa.lm = lm;
+  sa.pair_rt = G.pair_rt.p;
+  sa.pair_rt1 = G.pair_rt1.p;
+  sa.lvp4 = G.schur_lvp4.p;
+  sa.lvp = G.schur_lvp.p;
+  sa.rt_off = G.schur_rt_off;
+  return sa;
+}
+// … and the previous trial's accept with them: state ← candidate where the record says accepted (AcceptCopy)
+static void schur_accept_args(SchurArgs& sa, pba_engine* e) {
+  const GnData& G = e->gn;
+  sa.poses = e->poses.p;
+  sa.poses_new = G.poses_new.p;
+  sa.rho = e->rho.p;
+  sa.rho_new = G.rho_new.p;
+  sa.pt_orig = G.pt_orig.p;
+  sa.n_pose_d = 7 * e->n_frames;
+  sa.n_gn_points = G.n_gn_points;
+}
+
+// What assemble_kernel and export_band_kernel both read: the linearisation and Schur partials, the contribution lists,
+// the system's outputs, with the record lm.  Everything else zero, set by name where it is used.
+static AsmArgs asm_args(const GnData& G, const double* lm) {
+  AsmArgs a{};
+  a.part_lin = G.part_lin.p;
+  a.part_lin1 = G.part_lin1.p;
+  a.lm = lm;
+  a.part_schur = G.part_schur.p;
+  a.sky_cptr = G.sky_cptr.p;
+  a.sky_contrib = G.sky_contrib.p;
+  a.g_cptr = G.g_cptr.p;
+  a.g_contrib = G.g_contrib.p;
+  a.blk_i = G.sky_blk_i.p;
+  a.blk_j = G.sky_blk_j.p;
+  a.fixed = G.fixed.p;
+  a.S = G.S.p;
+  a.g = G.g.p;
+  a.g_dir = G.g_dir.p;
+  a.Ddiag = G.Ddiag.p;
+  a.n_sky = G.n_sky;
+  return a;
+}
+
 // Dynamic LDS above the default 64 KiB limit (the attribute is per device: set on every launch, cheap).
-void schur_lds_limit(const GnData& G) {
+static void schur_lds_limit(const GnData& G) {
   if (G.schur_lds > 65536)
     for (const void* f : {reinterpret_cast<const void*>(&schur_kernel), reinterpret_cast<const void*>(&schur_gate_kernel),
                           reinterpret_cast<const void*>(&schur_free_decide_kernel)})
@@ -1988,13 +1674,12 @@ void schur_lds_limit(const GnData& G) {
 // lm: the device LM record (λ, buffer set, done flag read on the device; lambda unused) or nullptr.
 // free_sets (the single-GPU LM loop without free intrinsics): the current set's λ-free partials, scaled in the assembly,
 // and schur_gate_kernel (the accept, the λ-specific elimination only for a degen set) instead of schur_kernel.
-int enqueue_solve(pba_engine* e, double lambda, const double* lm = nullptr, bool free_sets = false) {
+int enqueue_solve(pba_engine* e, double lambda, const double* lm, bool free_sets) {
   GnData& G = e->gn;
   const int nf = e->n_frames, nfs = G.nc_sys ? G.nfs : nf;
-  SchurArgs sa{G.schur_desc.p, G.schur_aux.p, G.schur_pairs.p, G.pt_fb.p, G.blk_lv.p,
-               G.blk_schur.p, G.blk_schur1.p, G.part_schur.p, G.pt_data.p, G.n_schur, lm ? lm : G.lm_idle.p,
-               lm ? e->poses.p : nullptr, G.poses_new.p, e->rho.p, G.rho_new.p, G.pt_orig.p, 7 * nf, G.n_gn_points,
-               G.pair_rt.p, G.pair_rt1.p, G.schur_lvp4.p, G.schur_lvp.p, G.schur_rt_off};
+  SchurArgs sa = schur_args(e, lm ? lm : G.lm_idle.p);
+  schur_accept_args(sa, e);
+  if (!lm) sa.poses = nullptr;  // a host-driven step: no accept to apply
   // free intrinsics: the elimination's launch also applies the previous trial's intrinsics accept (no launch of its own)
   const bool kacc = G.nc_sys && lm && !free_sets && G.n_schur > 0;
   if (kacc) {
@@ -2015,12 +1700,23 @@ int enqueue_solve(pba_engine* e, double lambda, const double* lm = nullptr, bool
   if (direct && G.cr0_dirty)  // a distributed solve rebuilt level 0 over the whole band: back to zeros + padding
     if (int rc = init_cr_level0(e)) return rc;
   CrLevel L0 = direct ? cr_level(G, 0) : CrLevel{};
-  AsmArgs aa{G.part_lin.p, G.part_lin1.p, lm ? lm : G.lm_idle.p, G.part_schur.p, G.sky_cptr.p, G.sky_contrib.p, G.g_cptr.p,
-             G.g_contrib.p, G.sky_blk_i.p, G.sky_blk_j.p, G.fixed.p, G.S.p, G.g.p, G.g_dir.p, G.Ddiag.p,
-             G.band_kernel && !direct ? G.Sband.p : nullptr, G.band_kernel, G.n_sky, nfs,
-             direct ? L0.D : nullptr, L0.U, L0.b, G.band_kernel, G.status.p, free_sets ? G.part_free0.p : nullptr,
-             free_sets ? G.part_free1.p : nullptr, free_sets ? G.degen.p : nullptr, G.sky_diag.p, G.sky_off.p,
-             G.n_sky_diag};
+  AsmArgs aa = asm_args(G, lm ? lm : G.lm_idle.p);
+  aa.Sband = G.band_kernel && !direct ? G.Sband.p : nullptr;
+  aa.band = G.band_kernel;
+  aa.n_frames = nfs;
+  aa.crD = direct ? L0.D : nullptr;
+  aa.crU = L0.U;
+  aa.crb = L0.b;
+  aa.crB = G.band_kernel;
+  aa.status = G.status.p;
+  if (free_sets) {
+    aa.part_free0 = G.part_free0.p;
+    aa.part_free1 = G.part_free1.p;
+    aa.degen = G.degen.p;
+  }
+  aa.sky_diag = G.sky_diag.p;
+  aa.sky_off = G.sky_off.p;
+  aa.n_diag = G.n_sky_diag;
   if (G.sband_dirty && G.band_kernel && !direct) {  // a distributed import filled the whole band: clear the off-profile part
     PBA_HIP(hipMemsetAsync(G.Sband.p, 0, sizeof(double) * (size_t)nf * ((G.band_kernel + 1) * 36 + 6), e->stream));
     G.sband_dirty = false;
@@ -2042,7 +1738,7 @@ int enqueue_solve(pba_engine* e, double lambda, const double* lm = nullptr, bool
 }
 
 // Schur complement for λ, assembly, solve and candidate state; returns the LM model decrease.
-int gn_step(pba_engine* e, double lambda, double* model_decrease, int* solver_status) {
+static int gn_step(pba_engine* e, double lambda, double* model_decrease, int* solver_status) {
   if (int rc = enqueue_solve(e, lambda)) return rc;
   double mp = 0.0, mq = 0.0;
   if (int rc = finish_step(e, lambda, e->gn.fixed.p, &mp, &mq, solver_status)) return rc;
@@ -2061,55 +1757,24 @@ void launch_accept(pba_engine* e, const double* lm) {
   e->pairs_fresh = false;
 }
 
-// Wait for trial `seq`'s decision record, published by lm_decide_kernel into host-coherent memory: a poll, not a
-// stream event (an event left the GPU idle ~6 µs each) — while the host polls, the GPU runs on into the gated accept
-// and linearisation.  The stream is queried now and then so a device error or a record that never comes ends the wait.
-double now_ms();
-constexpr double kDecisionTimeoutMs = 60000.0;  // one trial takes ~0.25 ms at C4
-
-int wait_decision(pba_engine* e, double seq, double* d) {
-  volatile double* r = e->gn.lm_h.p + rec_slot(seq);
-  // the stream is queried only after 2 ms without the record (a trial takes ~0.23 ms at C4), then every 2 ms: a
-  // hipStreamQuery every few hundred spins idled the GPU 5.7 µs before every trial's first kernel
-  // (profiles/r2_gn_trial_trace_v7.txt → v9)
-  // A device that stops making progress ends the wait after kDecisionTimeoutMs with PBA_ERR_DEVICE.
-  const double t0 = now_ms();
-  double next_query = t0 + 2.0;
-  for (unsigned spins = 1;; ++spins) {
-    if (r[kLmFields] == seq) break;
-    if ((spins & 255u) == 0u && now_ms() >= next_query) {
-      next_query = now_ms() + 2.0;
-      const hipError_t q = hipStreamQuery(e->stream);
-      if (q == hipSuccess && r[kLmFields] != seq) return fail(PBA_ERR_DEVICE, "LM decision record was not published");
-      if (q != hipSuccess && q != hipErrorNotReady) return fail(PBA_ERR_DEVICE, std::string("HIP: ") + hipGetErrorString(q));
-      if (next_query - t0 > kDecisionTimeoutMs)
-        return fail(PBA_ERR_DEVICE, "LM decision record not published within " + std::to_string(kDecisionTimeoutMs / 1000) + " s");
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  for (int i = 0; i < kLmFields; ++i) d[i] = r[i];
-  return PBA_OK;
+// A multi-GPU trial's first launch: the point elimination at the record's λ, which applies the previous trial's accept
+// first — or, on a rank without points, the accept alone.
+void launch_schur_accept(pba_engine* e, const double* lm) {
+  GnData& G = e->gn;
+  SchurArgs sa = schur_args(e, lm);
+  schur_accept_args(sa, e);
+  schur_lds_limit(G);
+  if (G.n_schur > 0) schur_kernel<<<G.n_schur, kBlockThreads, G.schur_lds, e->stream>>>(sa, 0.0);
+  else launch_accept(e, lm);
 }
 
-// One LM trial on a single GPU, enqueued whole and steered by the device LM record G.lm (λ, buffer set, done):
-// Schur complement + reduced solve → candidate state (poses, ρ, pair table) and model-decrease partials →
-// linearisation AT the candidate into the spare buffer set, whose per-chunk cost partials are the candidate cost →
-// the decision on the device (accept, the next trust radius, done; published to the host); the accept itself is applied
-// by the next trial's first kernel.  An accepted
-// step's linearisation is then already done (a rejected one cost a linearisation instead of a residual-only pass), and
-// since every kernel returns at once when the solve is done, the host enqueues the next trial before it has seen this
-// one's decision: no host round trip between trials.  The candidate is evaluated even when the solve failed (its
-// numbers are then discarded): a garbage state is memory-safe in every evaluation kernel.  ev (phase timing only,
-// else nullptr): begin | candidate state | candidate linearisation | decision.
 // The λ-free point elimination's launch after a linearisation (schur_free_decide_kernel): workgroup 0 the decision of
 // trial seq (init: the record of a new solve), the others the set's partials.
 void launch_free_decide(pba_engine* e, const DecideOpts& dopt, double seq, int gp, int gq, bool init, double radius) {
   GnData& G = e->gn;
-  const int nf = e->n_frames;
-  SchurArgs sa{G.schur_desc.p, G.schur_aux.p, G.schur_pairs.p, G.pt_fb.p, G.blk_lv.p,
-               G.blk_schur.p, G.blk_schur1.p, G.part_schur.p, G.pt_data.p, G.n_schur, G.lm.p,
-               nullptr, nullptr, nullptr, nullptr, nullptr, 7 * nf, G.n_gn_points,
-               G.pair_rt.p, G.pair_rt1.p, G.schur_lvp4.p, G.schur_lvp.p, G.schur_rt_off};
+  SchurArgs sa = schur_args(e, G.lm.p);  // (no accept here; the counts as the other launches of the loop pass them)
+  sa.n_pose_d = 7 * e->n_frames;
+  sa.n_gn_points = G.n_gn_points;
   DecideArgs da{G.red.p, G.red2.p, G.gmax.p, gp, gq, G.n_chunks, G.status.p, dopt, G.lm.p,
                 init ? nullptr : G.lm_host_d + rec_slot(seq), seq, init ? 1 : 0, radius, G.lm_init.p,
                 G.ts_part.p, G.ts_count.p};
@@ -2123,28 +1788,7 @@ void launch_free_decide(pba_engine* e, const DecideOpts& dopt, double seq, int g
 // free intrinsics keep the per-trial elimination (their border kernels read its point data at the trial's λ)
 bool lm_free_sets(const pba_engine* e) { return e->gn.nc_sys == 0 && e->gn.n_schur > 0; }
 
-int lm_trial(pba_engine* e, const DecideOpts& dopt, double seq, const hipEvent_t* ev) {
-  GnData& G = e->gn;
-  const bool fs = lm_free_sets(e);
-  if (ev) PBA_HIP(hipEventRecord(ev[0], e->stream));
-  if (int rc = enqueue_solve(e, 0.0, G.lm.p, fs)) return rc;
-  int gp = 0, gq = 0;
-  enqueue_updates(e, 0.0, G.fixed.p, &gp, &gq, G.lm.p, fs);
-  if (ev) PBA_HIP(hipEventRecord(ev[1], e->stream));
-  if (int rc = linearize(e, nullptr, G.lm.p, G.pairs_new.p, G.rho_new.p, G.red.p + 2 * (gp + gq), nullptr, true, fs))
-    return rc;
-  if (ev) PBA_HIP(hipEventRecord(ev[2], e->stream));
-  if (fs)
-    launch_free_decide(e, dopt, seq, gp, gq, false, 0.0);
-  else
-    lm_decide_kernel<<<1, kDecideThreads, 0, e->stream>>>(G.red.p, G.red2.p, G.gmax.p, gp, gq, G.n_chunks, G.status.p,
-                                                          dopt, G.lm.p, G.lm_host_d + rec_slot(seq), seq);
-  PBA_HIP(hipGetLastError());
-  if (ev) PBA_HIP(hipEventRecord(ev[3], e->stream));
-  return PBA_OK;  // an accepted candidate becomes the state in the next trial's first kernel (or after the loop)
-}
-
-int candidate_cost(pba_engine* e, double* cost) {
+static int candidate_cost(pba_engine* e, double* cost) {
   GnData& G = e->gn;
   if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC) {
     // the candidate poses straight into the fused-state prologue: no pair-table launch (C4: 32.4 → 29.8 µs for the
@@ -2159,7 +1803,7 @@ int candidate_cost(pba_engine* e, double* cost) {
   return total_cost(e, cost, nullptr);
 }
 
-int accept(pba_engine* e) {
+static int accept(pba_engine* e) {
   launch_accept(e, nullptr);
   PBA_HIP(hipGetLastError());
   return PBA_OK;
@@ -2175,7 +1819,7 @@ int exchange_K(pba_engine* e, int band, int* K) {
 
 // The exchange buffer: the keyframes' band rows (nf × ex_row(K)), with free intrinsics the 2·nc border rows
 // (nfs·36 + EX_TAIL each), then the kExScalars scalar slots of the device-steered loop.
-long long ex_border(const pba_engine* e) {
+static long long ex_border(const pba_engine* e) {
   const GnData& G = e->gn;
   return G.nc_sys ? 2LL * G.nc_sys * ((long long)G.nfs * 36 + EX_TAIL) : 0;
 }
@@ -2184,7 +1828,7 @@ long long exchange_count(pba_engine* e, int K) { return ex_scalar_off(e, K) + kE
 
 // The summed profile of a multi-GPU free-intrinsics solve (band K over the keyframes, border rows from frame 0): its
 // skyline layout and front_solve_kernel plan, built once per K.
-int ensure_dist_sky(pba_engine* e, int K) {
+static int ensure_dist_sky(pba_engine* e, int K) {
   GnData& G = e->gn;
   if (G.dsky_K == K) return PBA_OK;
   const int nf = e->n_frames, nfs = G.nfs;
@@ -2211,9 +1855,9 @@ int ensure_dist_sky(pba_engine* e, int K) {
 int enqueue_export(pba_engine* e, double lambda, const double* lm, double* X, int K) {
   GnData& G = e->gn;
   const int nf = e->n_frames;
-  AsmArgs aa{G.part_lin.p, G.part_lin1.p, lm, G.part_schur.p, G.sky_cptr.p, G.sky_contrib.p, G.g_cptr.p,
-             G.g_contrib.p, G.sky_blk_i.p, G.sky_blk_j.p, G.fixed.p, G.S.p, G.g.p, G.g_dir.p, G.Ddiag.p, nullptr, K,
-             G.n_sky, nf, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr};
+  AsmArgs aa = asm_args(G, lm);
+  aa.band = K;
+  aa.n_frames = nf;
   const long long n = (long long)nf * ex_row(K);  // (K+1)·36 band + EX_TAIL tail lanes per frame
   export_band_kernel<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(aa, G.observed.p, G.sky_first.p, G.sky_row.p,
                                                                         X, K);
@@ -2256,23 +1900,18 @@ int enqueue_import(pba_engine* e, double lambda, const double* lm, const double*
   return band_solve(e, !direct);
 }
 
-int step_export(pba_engine* e, double lambda, int band, double* X) {
+static int step_export(pba_engine* e, double lambda, int band, double* X) {
   GnData& G = e->gn;
   int K;
   if (int rc = exchange_K(e, band, &K)) return rc;
-  const int nf = e->n_frames;
-  SchurArgs sa{G.schur_desc.p, G.schur_aux.p, G.schur_pairs.p, G.pt_fb.p, G.blk_lv.p,
-               G.blk_schur.p, G.blk_schur1.p, G.part_schur.p, G.pt_data.p, G.n_schur, G.lm_idle.p,
-               nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
-               G.pair_rt.p, G.pair_rt1.p, G.schur_lvp4.p, G.schur_lvp.p, G.schur_rt_off};
+  const SchurArgs sa = schur_args(e, G.lm_idle.p);  // (a host-driven step: no accept, the counts 0)
   schur_lds_limit(G);
   if (G.n_schur > 0) schur_kernel<<<G.n_schur, kBlockThreads, G.schur_lds, e->stream>>>(sa, lambda);
-  (void)nf;
   return enqueue_export(e, lambda, G.lm_idle.p, X, K);
 }
 
-int step_import(pba_engine* e, double lambda, int band, const double* X, double* model_pose, double* model_points,
-                int* solver_status) {
+static int step_import(pba_engine* e, double lambda, int band, const double* X, double* model_pose,
+                       double* model_points, int* solver_status) {
   GnData& G = e->gn;
   int K;
   if (int rc = exchange_K(e, band, &K)) return rc;
@@ -2281,12 +1920,8 @@ int step_import(pba_engine* e, double lambda, int band, const double* X, double*
   return finish_step(e, lambda, G.fixed_dist.p, model_pose, model_points, solver_status);
 }
 
-
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-}  // namespace
+}  // namespace detail
+}  // namespace pba
 
 extern "C" {
 
@@ -2422,460 +2057,6 @@ int pba_gn_step_import(pba_engine* e, double lambda, int32_t band, const double*
   if (model_points) *model_points = mq;
   if (solver_status) *solver_status = st;
   return PBA_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// The collective of the multi-GPU loop: stream-ordered (a pba_comm: RCCL or an in-process group) or a host callback
-// that is called once the engine's stream has drained and is complete when it returns.
-struct Collective {
-  pba_allreduce_fn fn = nullptr;
-  void* user = nullptr;
-  pba_comm* comm = nullptr;
-  int allreduce(pba_engine* e, double* buf, long long n) const {
-    if (comm) return comm_allreduce(comm, buf, n, e->stream);
-    PBA_HIP(hipStreamSynchronize(e->stream));
-    if (int rc = fn(user, buf, n)) return fail(PBA_ERR_DEVICE, "allreduce callback failed (" + std::to_string(rc) + ")");
-    return PBA_OK;
-  }
-  // dist_sums_kernel's rank flag: 1 rank 0, 0 another rank, −1 unknown (a host callback without pba_gn_set_rank)
-  int rank0(const pba_engine* e) const {
-    const int r = comm ? comm_rank(comm) : e->gn.dist_rank;
-    return r < 0 ? -1 : (r == 0 ? 1 : 0);
-  }
-};
-
-// Levenberg-Marquardt (trust_region_minimizer.cc + levenberg_marquardt_strategy.cc semantics):
-// μ = 1/radius, step accepted when (cost − cost_new)/model_decrease > min_relative_decrease (1e-3);
-// success: radius /= max(1/3, 1 − (2ρ − 1)³), decrease factor 2; failure: radius /= factor, factor *= 2.
-// With a Reducer every cost, model decrease and the reduced system are sums over ranks, so all ranks take
-// the same decisions and the same pose steps.
-pba_solver_options lm_options(const pba_solver_options* o) {
-  pba_solver_options opt{};  // Ceres' defaults (solver.h:278-322), max_num_iterations as map_utils.h:318
-  opt.max_iterations = 20;
-  opt.max_num_consecutive_invalid_steps = 5;
-  opt.initial_trust_region_radius = 1e4;
-  opt.function_tolerance = 1e-6;
-  opt.parameter_tolerance = 1e-8;
-  opt.min_relative_decrease = 1e-3;
-  opt.gradient_tolerance = 1e-10;
-  opt.max_trust_region_radius = 1e16;
-  opt.min_trust_region_radius = 1e-32;
-  if (o) opt = *o;
-  if (opt.max_num_consecutive_invalid_steps <= 0) opt.max_num_consecutive_invalid_steps = 5;
-  return opt;
-}
-
-DecideOpts decide_opts(const pba_solver_options& o) {
-  return DecideOpts{o.min_relative_decrease, o.function_tolerance, o.parameter_tolerance, o.gradient_tolerance,
-                    o.max_trust_region_radius, o.min_trust_region_radius, o.max_num_consecutive_invalid_steps};
-}
-
-// The summary's outcome from a published decision record (done != 0).  Returns whether the trial counts as an
-// iteration (Ceres pushes no IterationSummary for a gradient-tolerance stop, which happens before the step, nor for the
-// consecutive-invalid-steps failure).
-bool finish_summary(double done, pba_solver_summary& s) {
-  switch ((int)done) {
-    case kDoneFunction: s.termination = PBA_TERMINATION_CONVERGENCE; s.stop_reason = PBA_STOP_FUNCTION_TOLERANCE; return true;
-    case kDoneParameter: s.termination = PBA_TERMINATION_CONVERGENCE; s.stop_reason = PBA_STOP_PARAMETER_TOLERANCE; return true;
-    case kDoneGradient: s.termination = PBA_TERMINATION_CONVERGENCE; s.stop_reason = PBA_STOP_GRADIENT_TOLERANCE; return false;
-    case kDoneRadius: s.termination = PBA_TERMINATION_CONVERGENCE; s.stop_reason = PBA_STOP_MIN_TRUST_REGION_RADIUS; return true;
-    default: s.termination = PBA_TERMINATION_FAILURE; s.stop_reason = PBA_STOP_INVALID_STEPS; return false;
-  }
-}
-
-// The trajectory of a solve, as Ceres' Solver::Summary::iterations (pba.h, pba_iteration_summary): entry 0 the initial
-// state, then one entry per trial Ceres pushes.  Filled from the published decision records as the host reads them; the
-// costs and cost changes are completed by finish() once the initial cost is known (pba_solve reads it after the loop).
-struct Trajectory {
-  std::vector<pba_iteration_summary>& it;
-  explicit Trajectory(std::vector<pba_iteration_summary>& v, double radius) : it(v) {
-    it.clear();
-    pba_iteration_summary z{};
-    z.step_is_successful = z.step_is_valid = 1;
-    z.trust_region_radius = radius;
-    z.gradient_max_norm = NAN;
-    it.push_back(z);
-  }
-  // trial record d (kLm* fields): its gradient is the one at the state the trial started from, i.e. the state the last
-  // entry ended in, if that entry has none yet (the initial state, an accepted step)
-  void trial(const double* d) {
-    if (std::isnan(it.back().gradient_max_norm)) it.back().gradient_max_norm = d[kLmGradNorm];
-    const double done = d[kLmDone];
-    if (done != 0.0 && done != kDoneRadius) return;  // a tolerance or the invalid-step limit: Minimize returns first
-    pba_iteration_summary x{};
-    x.iteration = (int)it.size();
-    x.step_is_valid = d[kLmStatus] == 0.0 && d[kLmModel] > 0.0;
-    x.step_is_successful = d[kLmAccept] != 0.0;
-    x.cost = d[kLmCostNew];  // (the candidate's; finish() puts the current cost on invalid steps)
-    x.relative_decrease = x.step_is_valid ? d[kLmRel] : 0.0;
-    x.trust_region_radius = d[kLmRadius];
-    x.step_norm = x.step_is_valid ? d[kLmStepNorm] : 0.0;
-    x.gradient_max_norm = x.step_is_successful ? NAN : it.back().gradient_max_norm;
-    it.push_back(x);
-  }
-  void finish(double initial_cost) {
-    double cur = initial_cost;
-    it[0].cost = initial_cost;
-    for (size_t k = 1; k < it.size(); ++k) {
-      pba_iteration_summary& x = it[k];
-      if (!x.step_is_valid) {
-        x.cost = cur;
-        x.cost_change = 0.0;
-        continue;
-      }
-      x.cost_change = cur - x.cost;
-      if (x.step_is_successful) cur = x.cost;
-    }
-  }
-};
-
-// Single GPU: every trial is enqueued whole (lm_trial) and the accept/reject decision is taken on the device, so
-// the host only reads the decision record back; the breakdown is device time between stream events.
-int lm_loop_single(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum) {
-  GnData& G = e->gn;
-  const pba_solver_options opt = lm_options(o);
-  pba_solver_summary s{};
-  struct Events {  // phase timing (pba_set_solver_timing): two sets of 4 (a trial is enqueued ahead)
-    hipEvent_t ev[8] = {};
-    ~Events() {
-      for (hipEvent_t x : ev)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } events;
-  const bool timed = G.phase_timing;
-  if (timed)
-    for (int i = 0; i < 8; ++i) PBA_HIP(hipEventCreate(&events.ev[i]));
-  const double t0 = now_ms();
-  double cost = 0.0;
-  // the initial linearisation (set 0) with its chunk cost partials in red, and the device record formed from them
-  // (lm_init_kernel): no host round trip before the first trial
-  const bool fs = lm_free_sets(e);
-  if (int rc = linearize(e, nullptr, nullptr, nullptr, nullptr, G.red.p, nullptr, false, fs)) return rc;
-  if (G.lm_init.n < 2) PBA_HIP(G.lm_init.resize(2));
-  if (fs)  // the record and set 0's λ-free partials in one launch
-    launch_free_decide(e, decide_opts(opt), 0.0, 0, 0, true, opt.initial_trust_region_radius);
-  else
-    lm_init_kernel<<<1, kDecideThreads, 0, e->stream>>>(G.red.p, G.n_chunks, opt.initial_trust_region_radius, G.lm.p,
-                                                         G.lm_init.p);
-  PBA_HIP(hipGetLastError());
-  for (int r = 0; r < kRecRing; ++r) G.lm_h[r * kRecStride + kLmFields] = 0.0;  // no trial published yet
-  // PBA_LM_HOST_DELAY_US (test build only, PBA_TEST_HOOKS): the host thread sleeps this long before each wait, as a
-  // descheduled thread would
-  const int delay_us = test_hook_int("PBA_LM_HOST_DELAY_US");
-  const int n = std::max(0, opt.max_iterations);
-  const DecideOpts dopt = decide_opts(opt);
-  auto enqueue = [&](int i) { return lm_trial(e, dopt, (double)(i + 1), timed ? events.ev + 4 * (i & 1) : nullptr); };
-  Trajectory traj(G.history, opt.initial_trust_region_radius);
-  if (n > 0)
-    if (int rc = enqueue(0)) return rc;
-  int iter = 0, set = 0;
-  s.termination = PBA_TERMINATION_MAX_ITERATIONS;
-  s.stop_reason = PBA_STOP_MAX_ITERATIONS;
-  for (; iter < n; ++iter) {
-    if (iter + 1 < n)
-      if (int rc = enqueue(iter + 1)) return rc;  // ahead of this trial's decision
-    if (delay_us > 0) std::this_thread::sleep_for(std::chrono::microseconds(delay_us));
-    double d[kLmFields];
-    if (int rc = wait_decision(e, (double)(iter + 1), d)) return rc;
-    set = (int)d[kLmSet];
-    traj.trial(d);
-    if (timed) {
-      const hipEvent_t* ev = events.ev + 4 * (iter & 1);
-      float ms = 0.0f;
-      PBA_HIP(hipEventSynchronize(ev[3]));
-      PBA_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-      s.solve_ms += ms;
-      PBA_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-      s.linearize_ms += ms;
-      PBA_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
-      s.cost_ms += ms;
-    }
-    s.gradient_max_norm = d[kLmGradNorm];
-    const double done = d[kLmDone];
-    if (done != 0.0 && done != kDoneRadius) {  // a tolerance (the step is not applied) or the invalid-step limit
-      if (finish_summary(done, s)) ++iter;
-      break;
-    }
-    if (d[kLmAccept] == 0.0) {  // invalid step (failed solve, no predicted decrease) or too little actual decrease
-      ++s.unsuccessful_steps;
-      if (done != 0.0) {  // the trust region collapsed
-        finish_summary(done, s);
-        ++iter;
-        break;
-      }
-      continue;
-    }
-    ++s.successful_steps;
-    cost = d[kLmCostNew];
-  }
-  launch_accept(e, G.lm.p);  // the last trial's accept (no trial after it to apply it)
-  double init[2] = {0.0, 0.0};
-  PBA_HIP(hipMemcpyAsync(init, G.lm_init.p, sizeof init, hipMemcpyDeviceToHost, e->stream));
-  PBA_HIP(hipStreamSynchronize(e->stream));
-  s.initial_cost = init[0];
-  traj.finish(init[0]);
-  if (s.successful_steps == 0) cost = init[0];
-  if (set == 1) {  // the current state's pieces are in set 1: make it set 0 for the host-driven entry points
-    std::swap(G.blk_schur.p, G.blk_schur1.p);
-    std::swap(G.blk_schur.n, G.blk_schur1.n);
-    std::swap(G.pair_rt.p, G.pair_rt1.p);
-    std::swap(G.pair_rt.n, G.pair_rt1.n);
-    std::swap(G.part_lin.p, G.part_lin1.p);
-    std::swap(G.part_lin.n, G.part_lin1.n);
-  }
-  s.iterations = iter;
-  s.final_cost = cost;
-  s.total_ms = now_ms() - t0;
-  if (sum) *sum = s;
-  return PBA_OK;
-}
-
-// One multi-GPU LM trial, enqueued whole on the engine stream and steered by the device LM record like lm_trial:
-// point elimination for the record's λ (the previous trial's accept applied first) → this rank's banded partial system
-// into X → Σ over ranks → damping, constant frames (requested, or observed by no rank), solve → candidate state and the
-// update partials → candidate linearisation into the spare buffer set (its chunk partials are this rank's candidate
-// cost) → this rank's trial sums, the point part Σ over ranks (kExScalars doubles) → the decision, the same on every
-// rank, published to the host.  Two collectives per trial: λ of trial i + 1 depends on the decision of trial i, and the
-// point elimination (hence this rank's system) on λ.  With a stream-ordered collective the host enqueues the next trial
-// before this one's decision is known, as on one GPU; every rank enqueues the same trials (the decisions agree), so the
-// collectives match.
-// PBA_TEST_PERTURB_DECISION = "rank:trial:mode" (tests): that rank's decision of that trial is overridden (mode 1: the
-// accept flag flipped, 2: the solve ended) — the ranks' records then differ, which the next trial's check must catch.
-struct DistCheck {
-  int n_ranks = 1;
-  double perturb_seq = -1.0;
-  int perturb_mode = 0;
-};
-
-int dist_trial(pba_engine* e, const Collective& coll, const DecideOpts& dopt, double* X, int K, double seq,
-               const DistCheck& chk) {
-  GnData& G = e->gn;
-  const int nf = e->n_frames;
-  SchurArgs sa{G.schur_desc.p, G.schur_aux.p, G.schur_pairs.p, G.pt_fb.p, G.blk_lv.p,
-               G.blk_schur.p, G.blk_schur1.p, G.part_schur.p, G.pt_data.p, G.n_schur, G.lm.p,
-               e->poses.p, G.poses_new.p, e->rho.p, G.rho_new.p, G.pt_orig.p, 7 * nf, G.n_gn_points,
-               G.pair_rt.p, G.pair_rt1.p, G.schur_lvp4.p, G.schur_lvp.p, G.schur_rt_off};
-  schur_lds_limit(G);
-  if (G.n_schur > 0) schur_kernel<<<G.n_schur, kBlockThreads, G.schur_lds, e->stream>>>(sa, 0.0);
-  else launch_accept(e, G.lm.p);  // no points on this rank: the accept alone
-  const long long nx = ex_scalar_off(e, K);  // the band rows and, with free intrinsics, the border rows
-  if (int rc = enqueue_export(e, 0.0, G.lm.p, X, K)) return rc;
-  if (int rc = coll.allreduce(e, X, nx)) return rc;
-  if (int rc = enqueue_import(e, 0.0, G.lm.p, X, K)) return rc;
-  int gp = 0, gq = 0;
-  enqueue_updates(e, 0.0, G.fixed_dist.p, &gp, &gq, G.lm.p);
-  if (G.n_chunks > 0)
-    if (int rc = linearize(e, nullptr, G.lm.p, G.pairs_new.p, G.rho_new.p, G.red.p + 2 * (gp + gq), nullptr, true))
-      return rc;  // (at the candidate intrinsics too)
-  double* Y = X + nx;
-  dist_sums_kernel<<<1, kDecideThreads, 0, e->stream>>>(G.red.p, G.red2.p, G.gmax.p, gp, gq, G.n_chunks, dopt.gtol,
-                                                         G.lm.p, G.status.p, coll.rank0(e), G.tpose.p, Y);
-  PBA_HIP(hipGetLastError());
-  if (int rc = coll.allreduce(e, Y, kExScalars)) return rc;
-  dist_decide_kernel<<<1, 64, 0, e->stream>>>(Y, G.tpose.p, coll.rank0(e) < 0 ? 1 : 0, dopt, G.lm.p,
-                                              G.lm_host_d + rec_slot(seq), seq, chk.n_ranks, chk.perturb_seq,
-                                              chk.perturb_mode, 0);
-  PBA_HIP(hipGetLastError());
-  return PBA_OK;
-}
-
-// The LM loop over one GPU (coll == nullptr) or all ranks: the host enqueues trial i + 1, then waits for the published
-// decision of trial i and builds Ceres' summary from it; after the loop the last accepted candidate becomes the state and
-// the current linearisation is moved to buffer set 0 for the host-driven entry points.
-int lm_loop(pba_engine* e, const pba_solver_options* o, const Collective* coll, double* X, int K, pba_solver_summary* sum) {
-  if (!coll) return lm_loop_single(e, o, sum);
-  GnData& G = e->gn;
-  const pba_solver_options opt = lm_options(o);
-  pba_solver_summary s{};
-  const double t0 = now_ms();
-  if (int rc = ensure_exchange_solver(e, K)) return rc;
-  double cost = 0.0;
-  int n_valid = 0;
-  if (int rc = linearize(e, &cost, nullptr, nullptr, nullptr, nullptr, &n_valid)) return rc;
-  DistCheck chk;
-  {  // Σ over ranks of the initial cost and valid blocks — and of 1: the number of ranks — through the scalar slots
-    double v[3] = {cost, (double)n_valid, 1.0};
-    double* Y = X + ex_scalar_off(e, K);
-    PBA_HIP(hipMemcpyAsync(Y, v, sizeof v, hipMemcpyHostToDevice, e->stream));
-    if (int rc = coll->allreduce(e, Y, 3)) return rc;
-    PBA_HIP(hipMemcpyAsync(v, Y, sizeof v, hipMemcpyDeviceToHost, e->stream));
-    PBA_HIP(hipStreamSynchronize(e->stream));
-    cost = v[0];
-    n_valid = (int)v[1];
-    chk.n_ranks = (int)v[2];
-  }
-  if (const char* pv = test_hook("PBA_TEST_PERTURB_DECISION")) {  // test build: "rank:trial:mode"
-    int pr = -1, pt = -1, pm = 1;
-    if (std::sscanf(pv, "%d:%d:%d", &pr, &pt, &pm) >= 2 && pr == (coll->comm ? comm_rank(coll->comm) : G.dist_rank)) {
-      chk.perturb_seq = pt;
-      chk.perturb_mode = pm;
-    }
-  }
-  s.linearize_ms = now_ms() - t0;
-  s.initial_cost = cost;
-  for (int i = 0; i < kRecRing * kRecStride; ++i) G.lm_h[i] = 0.0;  // (slot 0 stages the initial record below)
-  G.lm_h[kLmCost] = cost;
-  G.lm_h[kLmValid] = n_valid;
-  G.lm_h[kLmXNorm] = -1.0;
-  G.lm_h[kLmRadius] = opt.initial_trust_region_radius;
-  G.lm_h[kLmFactor] = 2.0;
-  G.lm_h[kLmLambda] = 1.0 / opt.initial_trust_region_radius;
-  PBA_HIP(hipMemcpyAsync(G.lm.p, G.lm_h.data(), sizeof(double) * kLmFields, hipMemcpyHostToDevice, e->stream));
-  const int n = std::max(0, opt.max_iterations);
-  const DecideOpts dopt = decide_opts(opt);
-  Trajectory traj(G.history, opt.initial_trust_region_radius);
-  int last_enq = 0;  // the last trial enqueued (collectives included)
-  if (n > 0) {
-    if (int rc = dist_trial(e, *coll, dopt, X, K, 1.0, chk)) return rc;
-    last_enq = 1;
-  }
-  int iter = 0, set = 0, stop_seq = 0;  // stop_seq: the trial whose record ended the loop
-  double stop_done = 0.0;
-  s.termination = PBA_TERMINATION_MAX_ITERATIONS;
-  s.stop_reason = PBA_STOP_MAX_ITERATIONS;
-  for (; iter < n; ++iter) {
-    if (iter + 1 < n) {
-      if (int rc = dist_trial(e, *coll, dopt, X, K, (double)(iter + 2), chk)) return rc;  // ahead of this decision
-      last_enq = iter + 2;
-    }
-    double d[kLmFields];
-    if (int rc = wait_decision(e, (double)(iter + 1), d)) return rc;
-    set = (int)d[kLmSet];
-    s.gradient_max_norm = d[kLmGradNorm];
-    const double done = d[kLmDone];
-    if (done == kDoneDesync) {
-      stop_seq = iter + 1;
-      stop_done = done;
-      break;
-    }
-    traj.trial(d);
-    if (done != 0.0 && done != kDoneRadius) {
-      stop_seq = iter + 1;
-      stop_done = done;
-      if (finish_summary(done, s)) ++iter;
-      break;
-    }
-    if (d[kLmAccept] == 0.0) {
-      ++s.unsuccessful_steps;
-      if (done != 0.0) {
-        stop_seq = iter + 1;
-        stop_done = done;
-        finish_summary(done, s);
-        ++iter;
-        break;
-      }
-      continue;
-    }
-    ++s.successful_steps;
-    cost = d[kLmCostNew];
-  }
-  // Every rank must leave with the same collectives issued.  Ranks whose records agree stop on the same trial; if they
-  // differed at trial k, the next trial's check ends the solve everywhere (kDoneDesync), but a rank whose record k said
-  // done has enqueued one trial fewer than a rank that went on (which enqueued k + 2 ahead): it reads record k + 1 (always
-  // published) and, when ranks went on, issues trial k + 2 too.  Then the last decision is checked by one more scalar
-  // all-reduce on every rank.
-  bool desync = stop_done == kDoneDesync;
-  int desync_at = desync ? stop_seq - 1 : 0;
-  if (!desync && stop_seq > 0 && last_enq > stop_seq) {
-    double d2[kLmFields];
-    if (int rc = wait_decision(e, (double)(stop_seq + 1), d2)) return rc;
-    if (d2[kLmDone] == kDoneDesync) {
-      desync = true;
-      desync_at = stop_seq;
-      const int stopped = (int)d2[kLmDesync] - 1;  // ranks whose record stop_seq ended the solve
-      if (stopped < chk.n_ranks && stop_seq + 2 <= n) {
-        if (int rc = dist_trial(e, *coll, dopt, X, K, (double)(stop_seq + 2), chk)) return rc;
-        last_enq = stop_seq + 2;
-      }
-    }
-  }
-  {
-    double* Y = X + ex_scalar_off(e, K);
-    dist_verify_kernel<<<1, 64, 0, e->stream>>>(G.lm.p, Y);
-    PBA_HIP(hipGetLastError());
-    if (int rc = coll->allreduce(e, Y, kExScalars)) return rc;
-    const double vseq = (double)(last_enq + 1);
-    dist_decide_kernel<<<1, 64, 0, e->stream>>>(Y, G.tpose.p, 1, dopt, G.lm.p, G.lm_host_d + rec_slot(vseq), vseq,
-                                                chk.n_ranks, -1.0, 0, 1);
-    PBA_HIP(hipGetLastError());
-    double d3[kLmFields];
-    if (int rc = wait_decision(e, vseq, d3)) return rc;
-    if (!desync && d3[kLmDone] == kDoneDesync) {
-      desync = true;
-      desync_at = last_enq;
-    }
-  }
-  launch_accept(e, G.lm.p);
-  PBA_HIP(hipStreamSynchronize(e->stream));
-  if (desync)
-    return fail(PBA_ERR_DEVICE, "multi-GPU solve: the ranks' LM decisions differed at trial " + std::to_string(desync_at) +
-                                    " (decision-word check); every rank ended the solve");
-  traj.finish(s.initial_cost);
-  if (set == 1) {
-    std::swap(G.blk_schur.p, G.blk_schur1.p);
-    std::swap(G.blk_schur.n, G.blk_schur1.n);
-    std::swap(G.pair_rt.p, G.pair_rt1.p);
-    std::swap(G.pair_rt.n, G.pair_rt1.n);
-    std::swap(G.part_lin.p, G.part_lin1.p);
-    std::swap(G.part_lin.n, G.part_lin1.n);
-  }
-  s.iterations = iter;
-  s.final_cost = cost;
-  s.total_ms = now_ms() - t0;
-  if (sum) *sum = s;
-  return PBA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum) {
-  if (int rc = ensure_prepared(e)) return rc;
-  return lm_loop(e, o, nullptr, nullptr, 0, sum);
-}
-
-int pba_solver_iterations(const pba_engine* e, int32_t capacity, pba_iteration_summary* out, int32_t* count) {
-  if (!e || !count || capacity < 0 || (capacity > 0 && !out)) return fail(PBA_ERR_INVALID_ARGUMENT, "bad arguments");
-  const std::vector<pba_iteration_summary>& h = e->gn.history;
-  const int n = std::min<int>(capacity, (int)h.size());
-  for (int i = 0; i < n; ++i) out[i] = h[i];
-  *count = (int)h.size();
-  return PBA_OK;
-}
-
-int pba_set_solver_timing(pba_engine* e, int32_t enable) {
-  if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
-  e->gn.phase_timing = enable != 0;
-  return PBA_OK;
-}
-
-int pba_solve_distributed(pba_engine* e, const pba_solver_options* o, int32_t band, double* d_exchange,
-                          pba_allreduce_fn allreduce, void* user, pba_solver_summary* sum) {
-  if (int rc = ensure_prepared(e)) return rc;
-  if (!d_exchange || !allreduce) return fail(PBA_ERR_INVALID_ARGUMENT, "null exchange buffer or allreduce");
-  int K;
-  if (int rc = exchange_K(e, band, &K)) return rc;
-  Collective c;
-  c.fn = allreduce;
-  c.user = user;
-  return lm_loop(e, o, &c, d_exchange, K, sum);
-}
-
-int pba_solve_distributed_comm(pba_engine* e, const pba_solver_options* o, int32_t band, pba_comm* comm,
-                               pba_solver_summary* sum) {
-  if (int rc = ensure_prepared(e)) return rc;
-  if (!comm) return fail(PBA_ERR_INVALID_ARGUMENT, "null communicator");
-  int K;
-  if (int rc = exchange_K(e, band, &K)) return rc;
-  GnData& G = e->gn;
-  PBA_HIP(G.exchange.resize((size_t)exchange_count(e, K)));
-  Collective c;
-  c.comm = comm;
-  return lm_loop(e, o, &c, G.exchange.p, K, sum);
 }
 
 }  // extern "C"
