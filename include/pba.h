@@ -171,16 +171,26 @@ int pba_record_bytes(const pba_engine* engine);
  * factor 2^−l; pba_set_intrinsics_state and pba_get_intrinsics speak of the level-0 state at every level.  The records
  * are fp32 only: with free intrinsics pba_set_record_format refuses the half formats, and with a half format active
  * this call refuses (PBA_ERR_INVALID_ARGUMENT either way; J_intr's distortion columns reach ~2.5e4 and a 21-value row
- * scale is a design of its own).  The on-device Gauss-Newton does not take photometric free intrinsics — its border
- * kernels are written for 2-row blocks — so every pba_gn_* entry point, pba_solve, pba_solve_pyramid and
- * pba_solve_distributed(_comm) returns PBA_ERR_INVALID_ARGUMENT instead of solving with the intrinsics held fixed; the
- * consumer is an outer solver over the records (include/pba_ceres.h, GpuPhotometricIntrinsicsCost).
+ * scale is a design of its own).  By default the on-device Gauss-Newton does not take photometric free intrinsics:
+ * every pba_gn_* entry point, pba_solve, pba_solve_pyramid and pba_solve_distributed(_comm) returns
+ * PBA_ERR_INVALID_ARGUMENT instead of solving with the intrinsics held fixed, and the consumer is an outer solver over
+ * the records (include/pba_ceres.h, GpuPhotometricIntrinsicsCost).  pba_gn_set_solve_intrinsics (below) opts the
+ * single-GPU entry points in: the state's 8 intrinsics per camera then join the reduced camera system as on a geometric
+ * engine (its border formed from 160-double moment records of the P-row blocks), pba_gn_accept and every
+ * solve that accepted a step leave the solved level-0 state in pba_get_intrinsics, and pba_solve_pyramid carries it
+ * across the levels.  The multi-GPU entry points (pba_gn_step_export/import, pba_solve_distributed(_comm)) refuse
+ * photometric free intrinsics either way.
  * Geometric engines: the on-device Gauss-Newton (pba_gn_*, pba_solve) then optimises the intrinsics too: each camera's 8
  * intrinsics are 12 unknowns of the reduced camera system after the keyframes' (two 6-dim blocks, the last four pads
  * with identity rows), a dense border of the skyline system (SPARSE_SCHUR keeps the intrinsics blocks among the f-blocks,
  * schur_complement_solver.cc:138-146); k ← k + δk, Ceres' LM diagonal over them too.  The multi-GPU entry points
  * exchange the border rows too (pba_gn_exchange_size). */
 int pba_set_optimize_intrinsics(pba_engine* engine, int32_t enable);
+/* Photometric engines with pba_set_optimize_intrinsics: let the on-device Gauss-Newton (pba_gn_linearize/step/
+ * candidate_cost/accept, pba_solve, pba_solve_pyramid) optimise the intrinsics state too — the arrow system of the
+ * geometric engines.  Default 0: those entry points refuse as before.  Geometric engines: PBA_OK, no effect (their
+ * solve always takes free intrinsics). */
+int pba_gn_set_solve_intrinsics(pba_engine* engine, int32_t enable);
 int pba_set_intrinsics_state(pba_engine* engine, const double* intrinsics);
 /* the intrinsics state (8·n_cams doubles: the free intrinsics with pba_set_optimize_intrinsics, else the cameras') */
 int pba_get_intrinsics(pba_engine* engine, double* intrinsics);

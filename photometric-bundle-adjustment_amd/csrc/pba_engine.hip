@@ -853,7 +853,7 @@ int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, dou
 
 extern "C" {
 
-int pba_version(void) { return 101; }
+int pba_version(void) { return 102; }
 
 const char* pba_status_string(int s) {
   switch (s) {
@@ -976,6 +976,25 @@ int upload_intrinsics_state(pba_engine* e) {
   return upload_cameras(e, e->n_cams, k.data(), e->intr_state, e->intr_state_d);
 }
 
+// The inverse: level-0 fx = fx_l·2^l, c = (c_l + 0.5)·2^l − 0.5 (photometric engines keep the level-0 state on the host).
+int download_intrinsics_state(pba_engine* e) {
+  if (!e->opt_intr || e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC || e->n_cams <= 0) return PBA_OK;
+  std::vector<double> k((size_t)kCamD * e->n_cams);
+  PBA_HIP(hipMemcpyAsync(k.data(), e->intr_state_d.p, sizeof(double) * k.size(), hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  const double s = std::ldexp(1.0, e->level);
+  e->intr_state_h.resize(8 * (size_t)e->n_cams);
+  for (int c = 0; c < e->n_cams; ++c) {
+    const double* r = k.data() + (size_t)kCamD * c;
+    double* o = e->intr_state_h.data() + 8 * (size_t)c;
+    for (int j = 0; j < 8; ++j) o[j] = r[j];
+    if (e->level > 0) {
+      o[0] = r[0] * s; o[1] = r[1] * s; o[2] = (r[2] + 0.5) * s - 0.5; o[3] = (r[3] + 0.5) * s - 0.5;
+    }
+  }
+  return PBA_OK;
+}
+
 }  // namespace detail
 }  // namespace pba
 
@@ -998,6 +1017,15 @@ int pba_set_optimize_intrinsics(pba_engine* e, int32_t enable) {
   e->pairs_fresh = false;  // (a photometric pair's target part is the state's)
   e->gn.prepared = false;  // the reduced camera system gains / loses its intrinsics border
   if (e->n_blocks > 0) PBA_HIP(e->out.resize((size_t)e->n_blocks * e->rec_floats()));
+  return PBA_OK;
+}
+
+int pba_gn_set_solve_intrinsics(pba_engine* e, int32_t enable) {
+  if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
+  if (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC) return PBA_OK;  // (a geometric solve always frees them)
+  const bool on = enable != 0;
+  if (on != e->gn_solve_intr) e->gn.prepared = false;  // the reduced camera system gains / loses its intrinsics border
+  e->gn_solve_intr = on;
   return PBA_OK;
 }
 

@@ -847,7 +847,17 @@ struct PoseUpdateArgs {
   const double* kcur;    // free intrinsics: the state's camera records (projection part) …
   double* knew_d;        // … the candidate's (camera records) …
   float* knew_f;         // … and their fp32 copy (8 per camera)
+  double kscale;         // 2^−level: the step is the level-0 state's, the records its image at the active level (entries
+                         // 0-3 move by 2^−level·δk₀, the distortion by δk₀); 1 at level 0 and on geometric engines
 };
+
+// Candidate intrinsics entry d of camera c — the one expression for intr_update_frame and the candidate pair table, so
+// both hold the same bits.
+__device__ __forceinline__ double candidate_intr(const PoseUpdateArgs& a, int c, int d) {
+  const int i = a.nf + 2 * c + (d >= 6), r = d - 6 * (d >= 6);
+  const double k = a.kcur[kCamD * c + d], xk = a.x[6 * i + r];
+  return a.fixed[i] ? k : k + (d < 4 ? a.kscale * xk : xk);
+}
 
 
 // Frame i's update inputs, all loaded in one memory round (every dependent round trip is ~1.7 µs in these kernels):
@@ -900,7 +910,7 @@ __device__ __forceinline__ void intr_update_frame(const PoseUpdateArgs& a, int i
     const int d = 6 * h + r;
     if (d >= 8) break;
     const double xk = a.x[6 * i + r], gk = a.g_dir[6 * i + r], Dk = a.Ddiag[6 * i + r];
-    const double k = a.kcur[kCamD * c + d], kn = fx ? k : k + xk;
+    const double k = a.kcur[kCamD * c + d], kn = candidate_intr(a, c, d);
     a.knew_d[kCamD * c + d] = kn;
     a.knew_f[8 * c + d] = (float)kn;
     if (fx) continue;
@@ -1089,6 +1099,8 @@ struct PairUpdateArgs {
   const double* cams;
   PairRec* pairs_new;  // nullptr: no candidate pair table (geometric engines form theirs in the cost path too)
   int n_pairs;
+  bool cand_tk;        // photometric free intrinsics: the target part is the CANDIDATE intrinsics' (candidate_intr; the
+                       // state's pair table carries the state, launch_pairs), not the cameras'
 };
 
 // The step's candidate state in ONE launch: workgroups [0, gp) update the poses (T·exp(δ)) and reduce the pose part
@@ -1129,7 +1141,7 @@ __global__ __launch_bounds__(kBlockThreads) void update_kernel(const PoseUpdateA
 #pragma unroll
     for (int j = 0; j < kCamK; ++j) {
       hk[j] = ra.cams[kCamD * pr.z + kCamHk + j];
-      tk[j] = ra.cams[kCamD * pr.w + j];
+      tk[j] = ra.cand_tk ? candidate_intr(pa, pr.w, j) : ra.cams[kCamD * pr.w + j];
     }
     if (lv.done != 0.0 || i >= ra.n_pairs) return;
     double H[7], T[7];
@@ -1352,8 +1364,8 @@ static int gn_prepare(pba_engine* e) {
   G.lpb = gn_lpb(e);
   G.ppl = gn_ppl(e);
   G.bpw = kBlockThreads / G.lpb;
-  // free intrinsics (geometric): nc cameras in the system
-  const int nc = (e->opt_intr && e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC) ? e->n_cams : 0;
+  // free intrinsics (geometric engines; photometric ones with pba_gn_set_solve_intrinsics): nc cameras in the system
+  const int nc = e->gn_free_intr() ? e->n_cams : 0;
   const GnPlanInput in{nf, e->n_cams, e->n_pairs, e->n_points, nb,
                        e->block_point_h.data(), e->block_target_h.data(), e->point_host_h.data(),
                        e->pair_of_h.data(), e->pair_host_h.data(), e->pair_target_h.data(), e->frame_cam_h.data(),
@@ -1375,7 +1387,8 @@ static int gn_prepare(pba_engine* e) {
   G.n_sky = P.n_sky;
   G.n_sky_diag = P.n_sky_diag;
   G.band = P.band;
-  G.ir_waves = P.ir_waves;
+  // (the photometric producer has no point-aligned form: its points' sums always come from intr_pw_kernel)
+  G.ir_waves = e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC ? 0 : P.ir_waves;
   const int ngp = P.n_gn_points, nfs = P.nfs;
   hipStream_t st = e->stream;
   if (int rc = build_front_plan(P.sky_first, P.sky_row, P.sky_colptr, P.sky_colrows, st, G.front, !in.skyline_global))
@@ -1390,7 +1403,7 @@ static int gn_prepare(pba_engine* e) {
     PBA_UP(ib_pptr);
     PBA_UP(ib_plist);
     PBA_UP(ib_pblk);
-    if (P.ir_waves) PBA_UP(ir_wave);
+    if (G.ir_waves) PBA_UP(ir_wave);
     if (int rc = intr_prepare_buffers(e)) return rc;
   }
   PBA_UP(lin_rec);
@@ -1483,14 +1496,15 @@ static int gn_prepare(pba_engine* e) {
   return PBA_OK;
 }
 
-int ensure_prepared(pba_engine* e) {
+int ensure_prepared(pba_engine* e, bool distributed) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
   if (e->n_blocks <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_blocks first");
   if (!e->state_set) return fail(PBA_ERR_NOT_READY, "pba_set_state first");
   if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC && (!e->have_images || e->P <= 0))
     return fail(PBA_ERR_NOT_READY, "images/pattern missing");
-  // the border kernels take 2-row (geometric) blocks: without this the solve would hold the intrinsics fixed (nc = 0)
-  if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC && e->opt_intr)
+  // without pba_gn_set_solve_intrinsics the solve would hold the intrinsics fixed (nc = 0): refused; the multi-GPU
+  // entry points (distributed) have no photometric border exchange and refuse either way
+  if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC && e->opt_intr && (!e->gn_solve_intr || distributed))
     return fail(PBA_ERR_INVALID_ARGUMENT,
                 "the on-device Gauss-Newton solve does not support free intrinsics on a photometric engine");
   if (int rc = check_device(e)) return rc;
@@ -1565,13 +1579,15 @@ void enqueue_updates(pba_engine* e, double lambda, const uint8_t* fixed, int* gp
   const int gq = (G.n_gn_points + kBlockThreads - 1) / kBlockThreads;
   const int gr = (e->n_pairs + kBlockThreads - 1) / kBlockThreads;
   const bool ki = G.nc_sys > 0;
+  const bool photo = e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC;
   PoseUpdateArgs pa{e->poses.p, G.x.p, G.g_dir.p, G.Ddiag.p, fixed, G.poses_new.p, G.red.p, G.red2.p, G.gmax.p, nfs, nf,
-                    ki ? e->intr_state_d.p : nullptr, ki ? G.intr_new_d.p : nullptr, ki ? G.intr_new_f.p : nullptr};
+                    ki ? e->intr_state_d.p : nullptr, ki ? G.intr_new_d.p : nullptr, ki ? G.intr_new_f.p : nullptr,
+                    photo ? std::ldexp(1.0, -e->level) : 1.0};
   // point workgroup q writes reduction slot gp + q, as the separate launches did
   PointUpdateArgs qa{G.pt_data.p, free_sets ? G.pt_data1.p : G.pt_data.p, G.pt_rec.p, G.pt_tgt.p, G.gn_target.p,
                      G.blk_schur.p, G.blk_schur1.p, G.x.p, fixed, e->rho.p, G.rho_new.p, G.drho.p, G.red.p,
                      G.red2.p, G.gmax.p, G.n_gn_points, ki ? G.ib_pw.p : nullptr, G.nc_sys, nf};
-  PairUpdateArgs ra{G.pair_rec.p, e->intr_d.p, G.pairs_new.p, e->n_pairs};
+  PairUpdateArgs ra{G.pair_rec.p, e->intr_d.p, G.pairs_new.p, e->n_pairs, ki && photo};
   update_kernel<<<gp + gq + gr, kBlockThreads, 0, e->stream>>>(pa, qa, ra, gp, gq, lambda, lm ? lm : G.lm_idle.p);
   G.pairs_new_fresh = true;
   *gp_out = gp;
@@ -1793,7 +1809,9 @@ static int candidate_cost(pba_engine* e, double* cost) {
   if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC) {
     // the candidate poses straight into the fused-state prologue: no pair-table launch (C4: 32.4 → 29.8 µs for the
     // cost launch, and the 7.6-µs pair launch gone)
-    if (int rc = launch_cost_only(e, G.pairs_new.p, G.rho_new.p, nullptr, nullptr, G.poses_new.p)) return rc;
+    if (int rc = launch_cost_only(e, G.pairs_new.p, G.rho_new.p, nullptr, nullptr, G.poses_new.p,
+                                  G.nc_sys ? G.intr_new_f.p : nullptr, G.nc_sys ? G.intr_new_d.p : nullptr))
+      return rc;
     return total_cost(e, cost, nullptr);
   }
   if (!G.pairs_new_fresh) launch_pairs(e, G.poses_new.p, G.pairs_new.p);
@@ -1806,6 +1824,8 @@ static int candidate_cost(pba_engine* e, double* cost) {
 static int accept(pba_engine* e) {
   launch_accept(e, nullptr);
   PBA_HIP(hipGetLastError());
+  // a photometric engine's host copy of the (level-0) intrinsics state follows the device state
+  if (e->gn.nc_sys) return download_intrinsics_state(e);
   return PBA_OK;
 }
 
@@ -2037,7 +2057,7 @@ int pba_gn_exchange_size(pba_engine* e, int32_t band, int64_t* count) {
 }
 
 int pba_gn_step_export(pba_engine* e, double lambda, int32_t band, double* d_exchange) {
-  if (int rc = ensure_prepared(e)) return rc;
+  if (int rc = ensure_prepared(e, true)) return rc;
   if (!d_exchange) return fail(PBA_ERR_INVALID_ARGUMENT, "null exchange buffer");
   if (!(lambda >= 0.0)) return fail(PBA_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
   if (int rc = step_export(e, lambda, band, d_exchange)) return rc;
@@ -2047,7 +2067,7 @@ int pba_gn_step_export(pba_engine* e, double lambda, int32_t band, double* d_exc
 
 int pba_gn_step_import(pba_engine* e, double lambda, int32_t band, const double* d_exchange, double* model_pose,
                        double* model_points, int32_t* solver_status) {
-  if (int rc = ensure_prepared(e)) return rc;
+  if (int rc = ensure_prepared(e, true)) return rc;
   if (!d_exchange) return fail(PBA_ERR_INVALID_ARGUMENT, "null exchange buffer");
   if (!(lambda >= 0.0)) return fail(PBA_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
   double mp = 0.0, mq = 0.0;

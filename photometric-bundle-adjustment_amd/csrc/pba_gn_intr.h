@@ -15,7 +15,8 @@ int intr_prepare_buffers(pba_engine* e);
 void launch_intr_accept(pba_engine* e, const double* lm);
 
 // The last trial's accept (lm: the LM record, else none; accept = false: the point elimination's launch has applied
-// it), then the weighted fp64 rows at the state.
+// it), then the blocks' contributions at the state: the weighted fp64 rows of a geometric engine, the moment records of a
+// photometric one (intr_rows_photometric_kernel).
 void enqueue_intr_rows(pba_engine* e, const double* lm, bool accept = true);
 
 // The border rows of the reduced system into the skyline S — or, X ≠ nullptr, this rank's undamped border into the

@@ -1,6 +1,6 @@
 // pba_gn_intr.hip — free intrinsics in the reduced camera system of a Gauss-Newton trial (pba_gn.hip): the weighted
-// fp64 rows (intr_rows_kernel), the points' camera sums (intr_pw_kernel), the border kernels (intr_border_*, intr_cam_*)
-// and the candidate intrinsics' accept (intr_accept_kernel), with their launchers (pba_gn_intr.h).  The part fused into
+// fp64 rows (intr_rows_kernel; photometric engines: the blocks' moment records, intr_rows_photometric_kernel), the points'
+// camera sums (intr_pw_kernel), the border kernels (intr_border_*, intr_cam_*) and the candidate intrinsics' accept (intr_accept_kernel), with their launchers (pba_gn_intr.h).  The part fused into
 // other kernels stays with them in pba_gn.hip: AcceptCopy (the elimination's launch applies the accept) and
 // intr_update_frame (update_kernel).  intr_cam_fin_build_kernel builds the arrow solve's level 0 with arrow_build
 // (pba_gn_solve.h).
@@ -32,6 +32,15 @@ namespace {
 // r (2), and W_i = J_iᵀJ_ρ (8)
 constexpr int kIbStride = 52;
 constexpr int kIbJi = 0, kIbJh = 16, kIbJt = 28, kIbJr = 40, kIbR = 42, kIbWi = 44;
+
+// ib_data per GN block of a PHOTOMETRIC engine (intr_rows_photometric_kernel): the second moments of the block's P weighted
+// rows [r | J_i (8) | J_h (6) | J_t (6) | J_ρ] that the border kernels use — 160 doubles whatever P (the rows themselves
+// would be 22·P): M_h = J_iᵀJ_h (8×6) | M_t = J_iᵀJ_t (8×6) | the upper triangle of J_iᵀJ_i (36) | J_iᵀr (8) |
+// W_i = J_iᵀJ_ρ (8) | w_h = J_hᵀJ_ρ (6) | w_t = J_tᵀJ_ρ (6)
+constexpr int kMomStride = 160;
+constexpr int kMomMh = 0, kMomMt = 48, kMomTri = 96, kMomJr = 132, kMomWi = 140, kMomWh = 148, kMomWt = 154;
+template <bool MOM>
+constexpr int kStrideOf = MOM ? kMomStride : kIbStride;
 
 struct IntrRowsArgs {
   const int4* rec;       // GN block → {block, point, host, target}
@@ -214,6 +223,129 @@ __global__ __launch_bounds__(256) void intr_rows_kernel(const IntrRowsArgs a) {
 #endif
 }
 
+// ---- the photometric producer --------------------------------------------------------------------------------------
+// The columns (ca, cb) of the staged row [r | J_i (1-8) | J_h (9-14) | J_t (15-20) | J_ρ (21)] whose product is moment m
+// of the record (kMom*).
+__device__ __forceinline__ int2 mom_cols(int m) {
+  if (m < kMomMt) return make_int2(1 + m / 6, 9 + m % 6);
+  if (m < kMomTri) return make_int2(1 + (m - kMomMt) / 6, 15 + (m - kMomMt) % 6);
+  if (m < kMomJr) {  // row i of the 8 × 8 upper triangle holds 8 − i entries (upper8i)
+    int i = 0, q = m - kMomTri;
+    while (q >= 8 - i) {
+      q -= 8 - i;
+      ++i;
+    }
+    return make_int2(1 + i, 1 + i + q);
+  }
+  if (m < kMomWi) return make_int2(1 + (m - kMomJr), 0);
+  if (m < kMomWh) return make_int2(1 + (m - kMomWi), 21);
+  if (m < kMomWt) return make_int2(9 + (m - kMomWh), 21);
+  return make_int2(15 + (m - kMomWt), 21);
+}
+
+struct IntrMomArgs {
+  const int4* rec;   // GN block → {block, point, host, target}
+  double* out;       // ib_data: kMomStride doubles per GN block
+  int n;             // GN blocks
+  const double* lm;  // LM record: nothing to do once the solve is done
+};
+
+// Eight lanes per GN block at the current state, eight blocks per wave (the linearisation's split): lane k evaluates
+// pattern pixels k, k + 8, … in ⌈P/8⌉ passes — photometric_row with INTR, the 22 columns of the record path (fp64 warp
+// and projection, fp32 chain; J_i columns 0-3 scaled by 2^−level), the block formed from the state's poses and the
+// intrinsics state (stage_tile's fused-state prologue) — and stages the pass's rows, unweighted and as doubles, in the
+// wave's LDS (a row that is not ok: zeros).  The wave's 8 × 160 moments are dealt over its lanes, 20 each, moment
+// o = lane + 64·i of the wave's record run: each is Σ over the block's rows in pixel order of the product of two staged
+// columns, in fp64 (the products of fp32 values are exact), a fixed order and no atomics.  The block's Corrector weight
+// ρ' from Σ r_k² and the Huber width (the linearisation's float arithmetic) then scales every moment (x̃ᵀỹ = ρ'·xᵀy); a
+// block the linearisation counts invalid (a pixel outside the projection domain or not finite) is zero.  The wave's
+// records are 1280 consecutive doubles: every store instruction writes 512 consecutive bytes.
+template <int PM>
+__global__ __launch_bounds__(256) void intr_rows_photometric_kernel(const KernelArgs a, const IntrMomArgs g) {
+  constexpr int LPB = 8, BW = 8, NM = kMomStride * BW / 64;  // 20 moments per lane
+  constexpr int kRowS = 23;  // doubles per staged row (22 used; odd: no systematic bank conflicts)
+  static_assert(kMomStride * BW % 64 == 0, "the wave's moments dealt evenly");
+  __shared__ __attribute__((aligned(16))) TileBlock s_tile[4][BW];
+  __shared__ double s_rows[4][64 * kRowS];
+  __shared__ float2 s_pat[4][PBA_MAX_PATTERN];
+  __shared__ float s_w[4][BW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, k = lane & (LPB - 1), wb = lane >> 3;
+  const int gb0 = (blockIdx.x * 4 + wave) * BW;
+  // (whole waves leave; everything below is private to the wave: no workgroup barrier)
+  if (gb0 >= g.n || lm_view(g.lm).done != 0.0) return;
+  const int nbw = min(BW, g.n - gb0);
+  const bool live = wb < nbw;
+  const int4 br = g.rec[live ? gb0 + wb : g.n - 1];  // a dead block evaluates the last block, masked below
+  const int P = a.P;
+  if (lane < PBA_MAX_PATTERN) s_pat[wave][lane] = pattern_at<PBA_MAX_PATTERN>(a, lane);
+  stage_tile<LPB>(a, s_tile[wave], wb, k, br.x, true);
+  // the moments of this lane: both columns' offsets in the staged rows of the moment's block
+  int off[NM];
+#pragma unroll
+  for (int i = 0; i < NM; ++i) {
+    const int o = lane + 64 * i, b = o / kMomStride;
+    const int2 c = mom_cols(o - kMomStride * b);
+    off[i] = (b * LPB * kRowS + c.x) | ((b * LPB * kRowS + c.y) << 16);
+  }
+  double acc[NM];
+#pragma unroll
+  for (int i = 0; i < NM; ++i) acc[i] = 0.0;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const TileBlock& tb = s_tile[wave][wb];
+  double* X = s_rows[wave];
+  int okl = 1;
+  float s = 0.0f;
+#pragma unroll 1
+  for (int px0 = 0; px0 < P; px0 += LPB) {
+    const int px = px0 + k;
+    const bool act = live && px < P;
+    const float Ih = act ? a.host_int[(long long)br.y * P + px] : 0.0f;
+    float ji[8];
+    const Row row = photometric_row<PM, true, TileBlock, false, true>(a, tb, s_pat[wave][act ? px : 0], Ih, nullptr, ji);
+    const bool use = act && row.ok;
+    okl &= act ? row.ok : 1;
+    s += use ? row.r * row.r : 0.0f;
+    auto xv = [&](float v) { return use ? (double)v : 0.0; };  // selects: a row that is not ok may hold inf / NaN
+    double* xr = X + lane * kRowS;
+    xr[0] = xv(row.r);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) xr[1 + j] = xv(ji[j]);
+    xr[9] = xv(row.hv.x); xr[10] = xv(row.hv.y); xr[11] = xv(row.hv.z);
+    xr[12] = xv(row.hw.x); xr[13] = xv(row.hw.y); xr[14] = xv(row.hw.z);
+    xr[15] = xv(row.tv.x); xr[16] = xv(row.tv.y); xr[17] = xv(row.tv.z);
+    xr[18] = xv(row.tw.x); xr[19] = xv(row.tw.y); xr[20] = xv(row.tw.z);
+    xr[21] = xv(row.jr);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int i = 0; i < NM; ++i) {
+      const double* xa = X + (off[i] & 0xffff);
+      const double* xb = X + (off[i] >> 16);
+#pragma unroll
+      for (int q = 0; q < LPB; ++q) acc[i] += xa[q * kRowS] * xb[q * kRowS];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // this pass's reads before the next pass's row stores
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  const int ok = group_all<LPB>(okl);
+  s = group_sum<LPB>(s);
+  if (k == 0) s_w[wave][wb] = live && ok ? huber_weight(s, a.huber) : 0.0f;  // (> 0 for a valid block)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  double* out = g.out + (long long)gb0 * kMomStride;
+#pragma unroll
+  for (int i = 0; i < NM; ++i) {
+    const int o = lane + 64 * i;
+    const float w = s_w[wave][o / kMomStride];
+    if (o < nbw * kMomStride) out[o] = w > 0.0f ? (double)w * acc[i] : 0.0;
+  }
+}
+
 struct IntrBorderArgs {
   const double* ib;        // ib_data
   const int4* ib_rec;      // GN block → {block, point, host, target}
@@ -244,6 +376,9 @@ struct IntrBorderArgs {
 // (every block of a point has the point's host).  The border kernels' Schur terms read these 8·nc + 6 values instead of
 // walking the point's blocks (4-5 × 52 doubles) once per (point, list) — at C4 that walk re-read the blocks' rows five
 // times per kernel, ≈ 0.4 GB per launch.  The same sums in the same order: the border is unchanged bit for bit.
+// MOM (here and in the border kernels): the blocks are moment records (photometric engines) — W_i and w_h are read, not
+// formed from two rows; the sums and their order are the same.
+template <bool MOM>
 __global__ __launch_bounds__(256) void intr_pw_kernel(const IntrBorderArgs a, int n_points) {
   // 8 lanes per point: lane k sums component k of every camera's W_c and (k < 6) of W_h, over the blocks in order
   const int t = blockIdx.x * blockDim.x + threadIdx.x, gp = t >> 3, k = t & 7;
@@ -255,12 +390,16 @@ __global__ __launch_bounds__(256) void intr_pw_kernel(const IntrBorderArgs a, in
   for (int c0 = 0; c0 < a.nc; c0 += 4) {  // cameras in groups of four (one pass over the blocks per group)
     double wc[4] = {0.0, 0.0, 0.0, 0.0};
     for (int b = pr.x; b < pr.x + pr.y; ++b) {
-      const double* B = a.ib + (long long)b * kIbStride;
+      const double* B = a.ib + (long long)b * kStrideOf<MOM>;
       const int cb = a.ib_cam[b] - c0;
-      const double w = B[kIbWi + k];
+      const double w = B[(MOM ? kMomWi : kIbWi) + k];
 #pragma unroll
       for (int c = 0; c < 4; ++c) wc[c] += c == cb ? w : 0.0;
-      if (c0 == 0 && k < 6) wh += B[kIbJh + k] * B[kIbJr] + B[kIbJh + 6 + k] * B[kIbJr + 1];
+      if constexpr (MOM) {
+        if (c0 == 0 && k < 6) wh += B[kMomWh + k];
+      } else {
+        if (c0 == 0 && k < 6) wh += B[kIbJh + k] * B[kIbJr] + B[kIbJh + 6 + k] * B[kIbJr + 1];
+      }
     }
     for (int c = 0; c < 4 && c0 + c < a.nc; ++c) o[8 * (c0 + c) + k] = wc[c];
   }
@@ -362,6 +501,7 @@ __device__ __forceinline__ double wave_rs48(const double (&v)[48], int lane, int
 // kpw = 4 while the keyframe waves would not fill the SIMDs (C3, 200 keyframes), else 2 (C4: 2008 waves; 1 and 4 measured
 // 80.5 and 82.4 against 76.5 µs).  Round 5 walked the lists twice (one kernel per border row: 133 + 117 µs at C4) and
 // each point's blocks once per (point, list).
+template <bool MOM>
 __device__ __forceinline__ void border_keyframes(const IntrBorderArgs& a, double lambda, int kpw, int bx, int by) {
   __shared__ double2 s_w[4][48];
   lambda = lm_lambda(lm_view(a.lm), lambda);
@@ -385,19 +525,27 @@ __device__ __forceinline__ void border_keyframes(const IntrBorderArgs& a, double
   for (; q < qb; q += dq) {
     const int bf = bn;
     if (q + dq < qb) bn = a.blist[q + dq];
-    const double* B = a.ib + (long long)(bf & 0x7fffffff) * kIbStride;
-    const double* Jc = B + (bf < 0 ? kIbJh : kIbJt);
-    double c0[6], c1[6];
+    const double* B = a.ib + (long long)(bf & 0x7fffffff) * kStrideOf<MOM>;
+    if constexpr (MOM) {  // the block's J_iᵀJ_h / J_iᵀJ_t, formed by the producer
+      const double* M = B + (bf < 0 ? kMomMh : kMomMt);
 #pragma unroll
-    for (int cc = 0; cc < 6; ++cc) {
-      c0[cc] = Jc[cc];
-      c1[cc] = Jc[6 + cc];
-    }
+      for (int d = 0; d < 8; ++d)
 #pragma unroll
-    for (int d = 0; d < 8; ++d) {
-      const double j0 = B[kIbJi + d], j1 = B[kIbJi + 8 + d];
+        for (int cc = 0; cc < 6; ++cc) acc[d][cc] += M[6 * d + cc];
+    } else {
+      const double* Jc = B + (bf < 0 ? kIbJh : kIbJt);
+      double c0[6], c1[6];
 #pragma unroll
-      for (int cc = 0; cc < 6; ++cc) acc[d][cc] += j0 * c0[cc] + j1 * c1[cc];
+      for (int cc = 0; cc < 6; ++cc) {
+        c0[cc] = Jc[cc];
+        c1[cc] = Jc[6 + cc];
+      }
+#pragma unroll
+      for (int d = 0; d < 8; ++d) {
+        const double j0 = B[kIbJi + d], j1 = B[kIbJi + 8 + d];
+#pragma unroll
+        for (int cc = 0; cc < 6; ++cc) acc[d][cc] += j0 * c0[cc] + j1 * c1[cc];
+      }
     }
   }
   int vi;
@@ -424,18 +572,24 @@ __device__ __forceinline__ void border_keyframes(const IntrBorderArgs& a, double
 #pragma unroll
       for (int cc = 0; cc < 6; ++cc) wy[cc] = pw[8 * a.nc + cc];
     } else if (by >= 0) {  // y is a target: the point's block targeting it
-      const double* B = a.ib + (long long)by * kIbStride;
+      const double* B = a.ib + (long long)by * kStrideOf<MOM>;
 #pragma unroll
-      for (int cc = 0; cc < 6; ++cc) wy[cc] = 0.0 + (B[kIbJt + cc] * B[kIbJr] + B[kIbJt + 6 + cc] * B[kIbJr + 1]);
+      for (int cc = 0; cc < 6; ++cc) {
+        if constexpr (MOM) wy[cc] = 0.0 + B[kMomWt + cc];
+        else wy[cc] = 0.0 + (B[kIbJt + cc] * B[kIbJr] + B[kIbJt + 6 + cc] * B[kIbJr + 1]);
+      }
     } else {  // several blocks of the point target y: their sum, in block order
       const int4 pr = a.pt_rec[gp];
 #pragma unroll
       for (int cc = 0; cc < 6; ++cc) wy[cc] = 0.0;
       for (int b = pr.x; b < pr.x + pr.y; ++b) {
         if (a.ib_rec[b].w != y) continue;
-        const double* B = a.ib + (long long)b * kIbStride;
+        const double* B = a.ib + (long long)b * kStrideOf<MOM>;
 #pragma unroll
-        for (int cc = 0; cc < 6; ++cc) wy[cc] += B[kIbJt + cc] * B[kIbJr] + B[kIbJt + 6 + cc] * B[kIbJr + 1];
+        for (int cc = 0; cc < 6; ++cc) {
+          if constexpr (MOM) wy[cc] += B[kMomWt + cc];
+          else wy[cc] += B[kIbJt + cc] * B[kIbJr] + B[kIbJt + 6 + cc] * B[kIbJr + 1];
+        }
       }
     }
     const double inv = border_inv(a, gp, lambda);
@@ -525,6 +679,7 @@ __device__ __forceinline__ void wg_sum_store(const double* acc, double* s_w, dou
   for (int i = threadIdx.x; i < NV; i += blockDim.x) out[i] = ((s_w[i] + s_w[NP + i]) + s_w[2 * NP + i]) + s_w[3 * NP + i];
 }
 
+template <bool MOM>
 __device__ __forceinline__ void cam_dir(const IntrBorderArgs& a, double* part, int bx, int by) {
   __shared__ double s_w[4 * pad16(kCamDir)];
   const int c = by, L = c * (a.nf + a.nc) + a.nf + c;  // (camera c, unit nf + c): every block of camera c
@@ -535,8 +690,14 @@ __device__ __forceinline__ void cam_dir(const IntrBorderArgs& a, double* part, i
   int q = a.bptr[L] + threadIdx.x + 256 * bx;
   int bn = q < qe ? a.blist[q] : 0;  // (the next entry's index loaded during this one)
   for (; q < qe; q += 256 * kCamSplit) {
-    const double* B = a.ib + (long long)bn * kIbStride;
+    const double* B = a.ib + (long long)bn * kStrideOf<MOM>;
     if (q + 256 * kCamSplit < qe) bn = a.blist[q + 256 * kCamSplit];
+    if constexpr (MOM) {  // the block's J_iᵀJ_i triangle and J_iᵀr, in cam_dir's accumulator order
+      static_assert(kMomJr == kMomTri + 36, "triangle then J_iᵀr: contiguous as the accumulators");
+#pragma unroll
+      for (int v = 0; v < kCamDir; ++v) acc[v] += B[kMomTri + v];
+      continue;
+    }
     double j0[8], j1[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -586,11 +747,13 @@ __device__ __forceinline__ void cam_sch(const IntrBorderArgs& a, double lambda, 
   wg_sum_store<kCamSch>(acc, s_w, part + ((long long)pc * kCamSplit + bx) * kCamSch);
 }
 
+template <bool MOM>
 __global__ __launch_bounds__(256) void intr_border_kernel(const IntrBorderArgs a, double lambda, int kpw) {
-  border_keyframes(a, lambda, kpw, blockIdx.x, blockIdx.y);
+  border_keyframes<MOM>(a, lambda, kpw, blockIdx.x, blockIdx.y);
 }
+template <bool MOM>
 __global__ __launch_bounds__(256) void intr_cam_dir_kernel(const IntrBorderArgs a, double* part) {
-  cam_dir(a, part, blockIdx.x, blockIdx.y);
+  cam_dir<MOM>(a, part, blockIdx.x, blockIdx.y);
 }
 __global__ __launch_bounds__(256) void intr_cam_sch_kernel(const IntrBorderArgs a, double lambda, double* part) {
   cam_sch(a, lambda, part, blockIdx.x, blockIdx.y);
@@ -601,17 +764,18 @@ __global__ __launch_bounds__(256) void intr_cam_sch_kernel(const IntrBorderArgs 
 // camera of direct sums, then kCamSplit per camera pair of Schur sums — instead of three launches in sequence, each a
 // fraction of the chip (C3: 35.3 → 24.6 µs, two cameras 41.3 → 31.1; at C4, where the keyframe part alone fills the
 // chip, side by side measured 108 against 102 µs in sequence).
+template <bool MOM>
 __global__ __launch_bounds__(256) void intr_border_all_kernel(const IntrBorderArgs a, double lambda, int kpw, int nk_x,
                                                              double* dpart, double* spart) {
   int b = blockIdx.x;
   const int nk = nk_x * a.nc, nd = kCamSplit * a.nc;
   if (b < nk) {
-    border_keyframes(a, lambda, kpw, b % nk_x, b / nk_x);
+    border_keyframes<MOM>(a, lambda, kpw, b % nk_x, b / nk_x);
     return;
   }
   b -= nk;
   if (b < nd) {
-    cam_dir(a, dpart, b % kCamSplit, b / kCamSplit);
+    cam_dir<MOM>(a, dpart, b % kCamSplit, b / kCamSplit);
     return;
   }
   b -= nd;
@@ -684,7 +848,9 @@ int intr_prepare_buffers(pba_engine* e) {
   GnData& G = e->gn;
   const int nb = e->n_blocks, ngp = G.n_gn_points, nc = G.nc_sys;
   hipStream_t st0 = e->stream;
-  PBA_HIP(G.ib_data.resize((size_t)nb * kIbStride));
+  // per GN block: the two weighted rows (geometric), or the moment record of its P rows (photometric)
+  const bool mom = e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC;
+  PBA_HIP(G.ib_data.resize((size_t)nb * (mom ? kMomStride : kIbStride)));
   PBA_HIP(G.ib_pw.resize((size_t)std::max(ngp, 1) * (8 * nc + 6)));
   PBA_HIP(G.ib_part.resize((size_t)kCamSplit * (nc * kCamDir + nc * (nc + 1) / 2 * kCamSch)));
   PBA_HIP(G.intr_new_d.resize((size_t)kCamD * nc));
@@ -701,9 +867,32 @@ void launch_intr_accept(pba_engine* e, const double* lm) {
                                                G.nc_sys);
 }
 
+// The photometric producer at the engine's state: the state's poses and inverse distances, the intrinsics state for the
+// target projection (make_kernel_args), the active level's images.
+template <int PM>
+static void launch_intr_rows_photometric(pba_engine* e, const KernelArgs& ka, const IntrMomArgs& ma) {
+  intr_rows_photometric_kernel<PM><<<(ma.n + 31) / 32, 256, 0, e->stream>>>(ka, ma);
+}
+
 void enqueue_intr_rows(pba_engine* e, const double* lm, bool accept) {
   GnData& G = e->gn;
   if (lm && accept) launch_intr_accept(e, lm);
+  if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC) {
+    KernelArgs ka = make_kernel_args(e, nullptr, e->rho.p);
+    ka.poses = e->poses.p;
+    const IntrMomArgs ma{G.ib_rec.p, G.ib_data.p, e->n_blocks, lm ? lm : G.lm_idle.p};
+    switch (e->opt.camera_model + 4 * e->interp) {  // PM = camera model + 4 · interpolator
+      case 0: launch_intr_rows_photometric<0>(e, ka, ma); break;
+      case 1: launch_intr_rows_photometric<1>(e, ka, ma); break;
+      case 2: launch_intr_rows_photometric<2>(e, ka, ma); break;
+      case 3: launch_intr_rows_photometric<3>(e, ka, ma); break;
+      case 4: launch_intr_rows_photometric<4>(e, ka, ma); break;
+      case 5: launch_intr_rows_photometric<5>(e, ka, ma); break;
+      case 6: launch_intr_rows_photometric<6>(e, ka, ma); break;
+      default: launch_intr_rows_photometric<7>(e, ka, ma); break;
+    }
+    return;
+  }
   IntrRowsArgs ra{G.ib_rec.p, e->poses.p, e->rho.p, e->u_ref.p, e->u_obs.p, e->frame_cam.p, e->intr_d.p,
                   e->intr_state_d.p, (double)e->opt.huber_width, G.ib_data.p, e->n_blocks, lm ? lm : G.lm_idle.p};
   int grid = (e->n_blocks + 255) / 256;
@@ -722,6 +911,22 @@ void enqueue_intr_rows(pba_engine* e, const double* lm, bool accept) {
   }
 }
 
+template <bool MOM>
+static void launch_border(pba_engine* e, const IntrBorderArgs& ba, double lambda, bool fused, int kpw, int nk_x, int ncp,
+                          double* dpart, double* spart) {
+  const GnData& G = e->gn;
+  if (G.ir_waves == 0)  // (else intr_rows_kernel has formed them)
+    intr_pw_kernel<MOM><<<(8 * G.n_gn_points + 255) / 256, 256, 0, e->stream>>>(ba, G.n_gn_points);
+  if (fused) {
+    const int n_wg = nk_x * G.nc_sys + kCamSplit * (G.nc_sys + ncp);
+    intr_border_all_kernel<MOM><<<n_wg, 256, 0, e->stream>>>(ba, lambda, kpw, nk_x, dpart, spart);
+  } else {
+    intr_border_kernel<MOM><<<dim3(nk_x, G.nc_sys), 256, 0, e->stream>>>(ba, lambda, kpw);
+    intr_cam_dir_kernel<MOM><<<dim3(kCamSplit, G.nc_sys), 256, 0, e->stream>>>(ba, dpart);
+    intr_cam_sch_kernel<<<dim3(kCamSplit, ncp), 256, 0, e->stream>>>(ba, lambda, spart);
+  }
+}
+
 void enqueue_border(pba_engine* e, double lambda, const double* lm, double* X, bool arrow) {
   GnData& G = e->gn;
   const int nf = e->n_frames, nfs = G.nfs;
@@ -729,8 +934,6 @@ void enqueue_border(pba_engine* e, double lambda, const double* lm, double* X, b
                     G.ib_pptr.p, G.ib_plist.p, G.sky_first.p, G.sky_row.p, G.fixed.p, lm ? lm : G.lm_idle.p, G.S.p,
                     G.g.p, G.g_dir.p, G.Ddiag.p, nf, G.nc_sys, X, (long long)nfs * 36 + EX_TAIL, G.ib_pw.p, G.ib_pblk.p};
   const int nb = 2 * G.nc_sys + 1;
-  if (G.ir_waves == 0)  // (else intr_rows_kernel has formed them)
-    intr_pw_kernel<<<(8 * G.n_gn_points + 255) / 256, 256, 0, e->stream>>>(ba, G.n_gn_points);
 #ifndef PBA_INTR_KPW_BIG
 #define PBA_INTR_KPW_BIG 2
 #endif
@@ -743,14 +946,9 @@ void enqueue_border(pba_engine* e, double lambda, const double* lm, double* X, b
   double* dpart = G.ib_part.p;
   double* spart = dpart + (size_t)G.nc_sys * kCamSplit * kCamDir;
   const int nk_x = (nf * kpw + 3) / 4, ncp = G.nc_sys * (G.nc_sys + 1) / 2;
-  if (fused) {
-    const int n_wg = nk_x * G.nc_sys + kCamSplit * (G.nc_sys + ncp);
-    intr_border_all_kernel<<<n_wg, 256, 0, e->stream>>>(ba, lambda, kpw, nk_x, dpart, spart);
-  } else {
-    intr_border_kernel<<<dim3(nk_x, G.nc_sys), 256, 0, e->stream>>>(ba, lambda, kpw);
-    intr_cam_dir_kernel<<<dim3(kCamSplit, G.nc_sys), 256, 0, e->stream>>>(ba, dpart);
-    intr_cam_sch_kernel<<<dim3(kCamSplit, ncp), 256, 0, e->stream>>>(ba, lambda, spart);
-  }
+  // the blocks as the producer left them: two weighted rows (geometric) or moment records (photometric)
+  if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC) launch_border<true>(e, ba, lambda, fused, kpw, nk_x, ncp, dpart, spart);
+  else launch_border<false>(e, ba, lambda, fused, kpw, nk_x, ncp, dpart, spart);
   const int fin_blocks = (2 * G.nc_sys * nb * 36 + 3) / 4;
   if (arrow) {
     const ArrowArgs aa = arrow_args(e, G.S.p, G.sky_first.p, G.sky_row.p, G.fixed.p);

@@ -254,7 +254,7 @@ constexpr int kDecideWgs = 16;
 constexpr int kExScalars = 16;
 
 // ---- pba_gn.hip: the stages of a trial, as the driver calls them ----
-int ensure_prepared(pba_engine* e);
+int ensure_prepared(pba_engine* e, bool distributed = false);  // distributed: a multi-GPU entry point
 int linearize(pba_engine* e, double* cost, const double* lm = nullptr, const PairRec* pairs = nullptr,
               const double* rho = nullptr, double* wg_red = nullptr, int* n_valid = nullptr, bool cand_intr = false,
               bool mark_set = false);

@@ -328,6 +328,9 @@ int solve_single(pba_engine* e, const pba_solver_options* o, pba_solver_summary*
   traj.finish(init[0]);
   if (s.successful_steps == 0) cost = init[0];
   current_set_to_0(G, lp.set);
+  // a photometric engine's host copy of the (level-0) intrinsics state follows the solved device state
+  if (G.nc_sys && s.successful_steps > 0)
+    if (int rc = download_intrinsics_state(e)) return rc;
   s.iterations = lp.iter;
   s.final_cost = cost;
   s.total_ms = now_ms() - t0;
@@ -521,7 +524,7 @@ int pba_set_solver_timing(pba_engine* e, int32_t enable) {
 
 int pba_solve_distributed(pba_engine* e, const pba_solver_options* o, int32_t band, double* d_exchange,
                           pba_allreduce_fn allreduce, void* user, pba_solver_summary* sum) {
-  if (int rc = ensure_prepared(e)) return rc;
+  if (int rc = ensure_prepared(e, true)) return rc;
   if (!d_exchange || !allreduce) return fail(PBA_ERR_INVALID_ARGUMENT, "null exchange buffer or allreduce");
   int K;
   if (int rc = exchange_K(e, band, &K)) return rc;
@@ -533,7 +536,7 @@ int pba_solve_distributed(pba_engine* e, const pba_solver_options* o, int32_t ba
 
 int pba_solve_distributed_comm(pba_engine* e, const pba_solver_options* o, int32_t band, pba_comm* comm,
                                pba_solver_summary* sum) {
-  if (int rc = ensure_prepared(e)) return rc;
+  if (int rc = ensure_prepared(e, true)) return rc;
   if (!comm) return fail(PBA_ERR_INVALID_ARGUMENT, "null communicator");
   int K;
   if (int rc = exchange_K(e, band, &K)) return rc;

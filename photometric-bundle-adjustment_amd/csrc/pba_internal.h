@@ -826,13 +826,15 @@ struct GnData {
   DevBuf<double> lm_init;    // the solve's initial cost and valid blocks (lm_init_kernel)
   DevBuf<double> lm_idle;    // the record host-driven steps pass to the kernels (not done, set 0, λ from the argument)
   PinnedBuf<double> lm_h;    // its host copy (+ sequence number), host-coherent, written by lm_decide_kernel
-  // Intrinsics in the reduced camera system (pba_set_optimize_intrinsics, geometric engines; pba_gn.hip "intrinsics"):
+  // Intrinsics in the reduced camera system (pba_set_optimize_intrinsics on geometric engines, and on photometric ones
+  // with pba_gn_set_solve_intrinsics; pba_gn.hip "intrinsics"):
   // camera c's 8 intrinsics are the system frames nf + 2c (dims 0-5) and nf + 2c + 1 (dims 6-7, four identity pads), a
   // dense border of the skyline system.  nc_sys = 0 without intrinsics; nfs = nf + 2·nc_sys system frames.
   int nc_sys = 0, nfs = 0;
   int dist_rank = -1;           // rank in a host-callback collective (pba_gn_set_rank); −1 unknown
   DevBuf<int4> ib_rec;          // GN block → {block, point, host, target}
-  DevBuf<double> ib_data;       // GN block → weighted fp64 rows [J_i (2×8) | J_h (2×6) | J_t (2×6) | J_ρ (2) | r (2) | W_i (8)]
+  DevBuf<double> ib_data;       // GN block → weighted fp64 rows [J_i (2×8) | J_h (2×6) | J_t (2×6) | J_ρ (2) | r (2) | W_i (8)];
+                                // photometric engines: the block's 160-double moment record (pba_gn_intr.hip)
   DevBuf<double> ib_pw;         // GN point → W_c (8 per camera), W_h (6): intr_pw_kernel
   DevBuf<int> ib_bptr, ib_blist;  // border unit pair (camera c, unit u) → GN blocks of its direct terms (CSR)
   DevBuf<int> ib_pptr, ib_plist;  // … → GN points of its Schur terms (CSR); unit u < nf: frame u, else camera u − nf
@@ -896,6 +898,7 @@ struct pba_engine {
   int interp = PBA_INTERP_BILINEAR;  // pba_set_interpolator
   bool host_int_sampled = false;     // I_h,k sampled on the device (pba_set_points without intensities)
   bool opt_intr = false;             // pba_set_optimize_intrinsics: target intrinsics state + J_intr record tail
+  bool gn_solve_intr = false;        // pba_gn_set_solve_intrinsics: a photometric engine's on-device solve frees them too
   pba::detail::DevBuf<float> intr_state;     // its projection constants (8 floats per camera) at the active level
   pba::detail::DevBuf<double> intr_state_d;  // and fp64 camera records (kCamD per camera)
   // photometric engines: the level-0 state as the caller set it (8 per camera); the device copy above is its image at
@@ -919,6 +922,8 @@ struct pba_engine {
   pba::detail::GnData gn;
 
   int R() const { return opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC ? P : 2; }
+  // the on-device Gauss-Newton solve carries the intrinsics state as unknowns (the border of the reduced system)
+  bool gn_free_intr() const { return opt_intr && (opt.residual_kind == PBA_RESIDUAL_GEOMETRIC || gn_solve_intr); }
   // values per record: [r | J_host | J_target | J_rho] (14R), + J_intr (8R) with pba_set_optimize_intrinsics
   int rec_floats() const { return (opt_intr ? 22 : 14) * R(); }
   // device bytes per record as stored: fp32 values, halves, or halves with the scale column (15R, pba.h)
@@ -956,6 +961,8 @@ int comm_size(const pba_comm* c);
 
 // The intrinsics state's device copy at the active pyramid level from intr_state_h (pba_engine.hip; photometric engines).
 int upload_intrinsics_state(pba_engine* e);
+// … and back: intr_state_h from the device copy (the level map inverted), after an on-device solve has moved the state.
+int download_intrinsics_state(pba_engine* e);
 
 // Pyramid (pba_pyramid.hip): back to level 0 and drop the levels; I_h,k sampled from the active level's host images.
 void reset_pyramid(pba_engine* e);

@@ -188,6 +188,7 @@ def lib(path: Optional[str] = None):
         "pba_comm_size": ([vp], C.c_int),
         "pba_comm_allreduce": ([vp, vp, C.c_int64, vp], C.c_int),
         "pba_set_optimize_intrinsics": ([vp, i32], C.c_int),
+        "pba_gn_set_solve_intrinsics": ([vp, i32], C.c_int),
         "pba_set_intrinsics_state": ([vp, vp], C.c_int),
         "pba_get_intrinsics": ([vp, vp], C.c_int),
         "pba_gn_system_size": ([vp, C.POINTER(i32)], C.c_int),
@@ -571,9 +572,16 @@ class Engine:
     def set_optimize_intrinsics(self, enable: bool = True):
         """Free target intrinsics: the target camera projects with the intrinsics state (set_intrinsics_state; it starts
         at the cameras' values), the host keeps the cameras', and the records grow to 22·R values with J_intr (R×8) as
-        their tail (split_record).  Photometric engines: fp32 records only, and the on-device solve refuses."""
+        their tail (split_record).  Photometric engines: fp32 records only, and the on-device solve refuses unless
+        gn_set_solve_intrinsics opts in."""
         self._ck(self._L.pba_set_optimize_intrinsics(self._h, int(bool(enable))), "pba_set_optimize_intrinsics")
         self.record = self._L.pba_record_floats(self._h)
+
+    def gn_set_solve_intrinsics(self, enable: bool = True):
+        """Photometric engines with set_optimize_intrinsics: the on-device Gauss-Newton (gn_linearize / gn_step /
+        gn_candidate_cost / gn_accept, solve, solve_pyramid) optimises the intrinsics state too.  Off by default (those
+        entry points refuse); no effect on a geometric engine, whose solve always takes free intrinsics."""
+        self._ck(self._L.pba_gn_set_solve_intrinsics(self._h, int(bool(enable))), "pba_gn_set_solve_intrinsics")
 
     def set_intrinsics_state(self, intrinsics: np.ndarray):
         """(n_cams, 8) level-0 intrinsics; at a pyramid level the engine projects with their image at that level."""
