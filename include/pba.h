@@ -123,7 +123,8 @@ int pba_synchronize(pba_engine* engine);
 
 /* Results ---------------------------------------------------------------------------------------- */
 /* values per record as pba_get_records returns them: 14·R, or — with pba_set_optimize_intrinsics, on geometric and
- * photometric engines alike — 22·R: [ r(R) | J_host(R×6) | J_target(R×6) | J_rho(R) | J_intr(R×8) ] */
+ * photometric engines alike — 22·R: [ r(R) | J_host(R×6) | J_target(R×6) | J_rho(R) | J_intr(R×8) ], or — with
+ * pba_set_affine_brightness — 18·R: [ … | J_rho(R) | J_ab_host(R×2) | J_ab_target(R×2) ] */
 int pba_record_floats(const pba_engine* engine);
 /* Record storage format (photometric engines): PBA_RECORD_F32 (default) or PBA_RECORD_F16 — IEEE half records,
  * half the HBM write traffic (config C5's "fp16 residuals"; evaluation stays fp64 warp + fp32 chain, rounding
@@ -151,7 +152,7 @@ int pba_set_record_format(pba_engine* engine, int32_t format);
 int pba_record_format(const pba_engine* engine);
 /* device bytes per record as stored: 4·pba_record_floats (PBA_RECORD_F32), 28·R (PBA_RECORD_F16) or 30·R
  * (PBA_RECORD_F16_SCALED).  pba_record_floats stays 14·R in the half formats: it describes what pba_get_records returns.
- * With pba_set_optimize_intrinsics the records are fp32 only: 88·R bytes. */
+ * With pba_set_optimize_intrinsics the records are fp32 only: 88·R bytes; with pba_set_affine_brightness 72·R. */
 int pba_record_bytes(const pba_engine* engine);
 /* Target-intrinsics Jacobian (geometric and photometric engines; BundleAdjustmentOptions::optimize_intrinsics,
  * map_utils.h:339-345):
@@ -194,6 +195,39 @@ int pba_gn_set_solve_intrinsics(pba_engine* engine, int32_t enable);
 int pba_set_intrinsics_state(pba_engine* engine, const double* intrinsics);
 /* the intrinsics state (8·n_cams doubles: the free intrinsics with pba_set_optimize_intrinsics, else the cameras') */
 int pba_get_intrinsics(pba_engine* engine, double* intrinsics);
+/* Affine brightness per keyframe (photometric engines; the transform [a, b] of Engel et al.'s direct sparse odometry
+ * that PhotometricError<8> names as left out, photometric_error.h:61-63).  Every keyframe f has two parameters
+ * (a_f, b_f), held by the engine as the affine state [a_0 b_0 a_1 b_1 …] of 2·n_frames doubles.  Enabled, with h the
+ * block's host keyframe, t its target and E = exp(a_t − a_h),
+ *   r_k = (I_t(π(p̃_k)) − b_t) − E·(I_h,k − b_h)                                   k < R
+ * and each record grows by four columns per pixel row after J_rho, 18·R values (72·R bytes, fp32 only):
+ *   [ r(R) | J_host(R×6) | J_target(R×6) | J_rho(R) | J_ab_host(R×2) | J_ab_target(R×2) ]
+ *   row k:  J_ab_host   = [ ∂r/∂a_h, ∂r/∂b_h ] = [ +E·(I_h,k − b_h), +E ]
+ *           J_ab_target = [ ∂r/∂a_t, ∂r/∂b_t ] = [ −E·(I_h,k − b_h), −1 ]
+ * J_host, J_target and J_rho are unchanged (∇I_t does not depend on (a, b)); the records stay unrobustified and the
+ * per-block Huber cost (pba_get_block_costs, pba_get_cost) is taken on the new r.  a_t − a_h and its exponential are
+ * formed in fp64 from the state once per block; E, b_h, b_t are floats from there on, and at a = b = 0 the residual is
+ * I − I_h bit for bit.  Validity is unchanged (projection domain, finite values): a non-finite a or b of a block's host
+ * or target makes the block invalid, its record 18·R zeros; a residual-only evaluation writes r at the 18·R stride.
+ * (a, b) are shared by all pyramid levels (the 2×2 mean is linear in intensity: no level factor).  Every read-back
+ * path serves the 18·R records (pba_get_records, _raw, _async / pba_wait_records, pba_get_residuals,
+ * pba_device_records, pba_decode_records_device).
+ * pba_set_affine_brightness: enabling sets the state to zeros, disabling restores the 14·R records.  Refused with
+ * PBA_ERR_INVALID_ARGUMENT, the engine left as it was: on a geometric engine; with a half record format active (and
+ * pba_set_record_format then refuses the half formats: the brightness columns have no half layout); together with
+ * pba_set_optimize_intrinsics, whichever comes second (a 26-column record is not built).  While it is enabled every
+ * on-device Gauss-Newton entry point (pba_gn_*, pba_solve, pba_solve_pyramid, pba_gn_step_export/import,
+ * pba_solve_distributed(_comm)) returns PBA_ERR_INVALID_ARGUMENT: its linearisation evaluates the rows itself and
+ * would solve with a = b = 0.  The consumer is an outer solver over the records (include/pba_ceres.h,
+ * GpuPhotometricAffineCost).
+ * pba_set_affine_state / _device (host / device memory) and pba_get_affine_state move the 2·n_frames doubles;
+ * PBA_ERR_NOT_READY before pba_set_frames or without pba_set_affine_brightness.  pba_set_frames* resets the state to
+ * zeros.  pba_evaluate_state(s)_device keep taking poses and inverse distances only: the affine state is the engine's,
+ * as the intrinsics state is. */
+int pba_set_affine_brightness(pba_engine* engine, int32_t enable);
+int pba_set_affine_state(pba_engine* engine, const double* ab);
+int pba_set_affine_state_device(pba_engine* engine, const double* d_ab);
+int pba_get_affine_state(pba_engine* engine, double* ab);
 /* Image interpolator of the photometric residual (and of the device-sampled I_h,k): PBA_INTERP_BILINEAR (default,
  * the north star's) or PBA_INTERP_BICUBIC — Ceres' BiCubicInterpolator over Grid2D<uint8_t, 1>
  * (cubic_interpolation.h:252-344, edge clamp :403-414), the interpolator of PhotometricError<8>

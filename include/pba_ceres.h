@@ -29,6 +29,11 @@
 //     GpuReprojectionCost and GpuPhotometricIntrinsicsCost<P> hand to Ceres as the fourth parameter block's Jacobian.
 //     Without the blocks, a Jacobian request for an intrinsics block is refused: that Evaluate returns false and Ceres
 //     stops with FAILURE instead of optimising with a zero gradient.
+//   * Affine brightness (photometric): given one (a, b) parameter block of 2 doubles per keyframe, the evaluator enables
+//     pba_set_affine_brightness and uploads the blocks' current values before every evaluation (pba_set_affine_state);
+//     r_k = (I_t − b_t) − exp(a_t − a_h)·(I_h,k − b_h), and the records' tail J_ab_host, J_ab_target (R×2 each) is what
+//     GpuPhotometricAffineCost<P> hands to Ceres for its fourth and fifth parameter blocks.  Without the blocks a
+//     Jacobian request for one of them is refused like an intrinsics one.  Not combined with the intrinsics blocks.
 //
 // The loss function stays with Ceres (HuberLoss is applied after Evaluate, residual_block.cc:161-196).
 // Requires <ceres/ceres.h> (Ceres ≥ 2.0, which has EvaluationCallback) and include/pba.h on the include path.
@@ -183,13 +188,19 @@ class GpuEvaluator : public ceres::EvaluationCallback {
   // inv_dist[p] = &landmark.inv_depth of point p; intrinsics[c] = calib_cam.intrinsics[c]->data() (8 doubles) when the
   // problem's intrinsics blocks may be free (optimize_intrinsics; geometric or photometric engine), else empty.  The
   // engine must already hold the problem structure.
+  // affine[f] = the (a_f, b_f) block of keyframe f (2 doubles) when the photometric problem carries affine brightness
+  // blocks (GpuPhotometricAffineCost), else empty; one per keyframe, not together with `intrinsics`.
   GpuEvaluator(pba_engine* engine, std::vector<double*> poses, std::vector<double*> inv_dist,
-               std::vector<double*> intrinsics = {}, PoseJacobian pose_jacobian = PoseJacobian::kReferenceSE3)
+               std::vector<double*> intrinsics = {}, PoseJacobian pose_jacobian = PoseJacobian::kReferenceSE3,
+               std::vector<double*> affine = {})
       : engine_(engine), poses_(std::move(poses)), rho_(std::move(inv_dist)), intr_(std::move(intrinsics)),
-        form_(pose_jacobian) {
+        ab_(std::move(affine)), form_(pose_jacobian) {
     if (pba_record_format(engine_) != PBA_RECORD_F32)
       throw std::runtime_error("pba_ceres: fp16 records saturate at ±65504; the adapter needs PBA_RECORD_F32");
+    if (!ab_.empty() && ab_.size() != poses_.size())
+      throw std::runtime_error("pba_ceres: one affine brightness block per keyframe");
     if (!intr_.empty()) check(pba_set_optimize_intrinsics(engine_, 1), "pba_set_optimize_intrinsics");
+    if (!ab_.empty()) check(pba_set_affine_brightness(engine_, 1), "pba_set_affine_brightness");
     R_ = pba_residuals_per_block(engine_);
     rec_ = pba_record_floats(engine_);
     // the page-locked read-back and state buffers are allocated (and mapped for the device) here, with the problem,
@@ -204,7 +215,7 @@ class GpuEvaluator : public ceres::EvaluationCallback {
 
   // Called on the solver thread after Ceres has written the evaluation point into the user's parameter memory
   // (program_evaluator.h:157-162).  A Jacobian evaluation reads back the whole records; a residual-only one (the
-  // LM candidate, trust_region_minimizer.cc:761-779) only the residuals, R of every 14R (22R) record values.  The
+  // LM candidate, trust_region_minimizer.cc:761-779) only the residuals, R of every 14R (22R, 18R) record values.  The
   // evaluation after an accepted step comes with new_evaluation_point = false (trust_region_minimizer.cc:805-822):
   // when the point was already evaluated with Jacobians nothing is recomputed.
   // Where PrepareForEvaluation's time goes (seconds, summed over calls; [0] residual-only, [1] with Jacobians):
@@ -240,6 +251,11 @@ class GpuEvaluator : public ceres::EvaluationCallback {
       state_k_.resize(8 * intr_.size());
       for (size_t c = 0; c < intr_.size(); ++c) std::memcpy(&state_k_[8 * c], intr_[c], 8 * sizeof(double));
       check(pba_set_intrinsics_state(engine_, state_k_.data()), "pba_set_intrinsics_state");
+    }
+    if (!ab_.empty()) {
+      state_ab_.resize(2 * ab_.size());
+      for (size_t f = 0; f < ab_.size(); ++f) std::memcpy(&state_ab_[2 * f], ab_[f], 2 * sizeof(double));
+      check(pba_set_affine_state(engine_, state_ab_.data()), "pba_set_affine_state");
     }
     const auto t1 = clk::now();
     check(pba_evaluate(engine_, evaluate_jacobians ? 1 : 0), "pba_evaluate");
@@ -303,11 +319,15 @@ class GpuEvaluator : public ceres::EvaluationCallback {
   bool valid(int block) const { return valid_src_[block] != 0; }
   bool has_jacobians() const { return have_jac_; }
   bool has_intrinsics() const { return !intr_.empty(); }
+  bool has_affine() const { return !ab_.empty(); }
   PoseJacobian pose_jacobian() const { return form_; }
   const double* pose_pinv(int frame) const { return pinv_src_ + 42 * (size_t)frame; }  // P⁺ (6×7) at the prepared point
   // a Jacobian was requested for an intrinsics block the evaluator was not given (Evaluate returned false)
   bool refused_intrinsics() const { return refused_.load(); }
   void refuse_intrinsics() const { refused_.store(true); }
+  // the same for an affine brightness block
+  bool refused_affine() const { return refused_ab_.load(); }
+  void refuse_affine() const { refused_ab_.store(true); }
 
  protected:
   // What Evaluate reads (record / residuals / valid / pose_pinv): the read-back buffers below after a
@@ -317,12 +337,12 @@ class GpuEvaluator : public ceres::EvaluationCallback {
   const uint8_t* valid_src_ = nullptr;
   const double* pinv_src_ = nullptr;
   pba_engine* engine_;
-  std::vector<double*> poses_, rho_, intr_;
+  std::vector<double*> poses_, rho_, intr_, ab_;
   PoseJacobian form_;
   bool async_ = false;
-  std::vector<double> state_k_, pinv_;
+  std::vector<double> state_k_, state_ab_, pinv_;
   PinnedArray<double> state_p_, state_r_;
-  mutable std::atomic<bool> refused_{false};
+  mutable std::atomic<bool> refused_{false}, refused_ab_{false};
   mutable std::atomic<long long> wait_ns_{0};
   PrepareTimes times_;
   PinnedArray<float> records_, residuals_;
@@ -413,6 +433,35 @@ class GpuPhotometricIntrinsicsCost : public ceres::SizedCostFunction<P, 7, 7, 1,
       : ev_(ev), block_(block), host_(host), target_(target) {}
   bool Evaluate(double const* const* /*parameters*/, double* residuals, double** jacobians) const override {
     return copy_block<P>(*ev_, block_, host_, target_, residuals, jacobians, 8);
+  }
+
+ private:
+  const GpuEvaluator* ev_;
+  int block_, host_, target_;
+};
+
+// Photometric block with affine brightness: SizedCostFunction<P, 7, 7, 1, 2, 2> over (T_w_host, T_w_target, ρ, ab_host,
+// ab_target), ab = (a, b) of the keyframe.  jacobians[3] = J_ab_host (P×2 row-major, [E·(I_h − b_h), E]) and
+// jacobians[4] = J_ab_target ([−E·(I_h − b_h), −1]) are the record's tail; either may be null (a constant block, such
+// as the gauge keyframe's), which leaves the first three blocks unchanged.  The evaluator must have been given the
+// (a, b) blocks: else a request for jacobians[3] or [4], and only that, is refused (refused_affine()).
+template <int P>
+class GpuPhotometricAffineCost : public ceres::SizedCostFunction<P, 7, 7, 1, 2, 2> {
+ public:
+  GpuPhotometricAffineCost(const GpuEvaluator* ev, int block, int host, int target)
+      : ev_(ev), block_(block), host_(host), target_(target) {}
+  bool Evaluate(double const* const* /*parameters*/, double* residuals, double** jacobians) const override {
+    if (jacobians && (jacobians[3] || jacobians[4]) && !ev_->has_affine()) {
+      ev_->refuse_affine();
+      return false;
+    }
+    if (!copy_block<P>(*ev_, block_, host_, target_, residuals, jacobians, 0)) return false;
+    if (!jacobians) return true;
+    const float* rec = ev_->record(block_);
+    for (int q = 0; q < 2; ++q)
+      if (jacobians[3 + q])
+        for (int i = 0; i < 2 * P; ++i) jacobians[3 + q][i] = rec[(14 + 2 * q) * P + i];
+    return true;
   }
 
  private:

@@ -136,14 +136,18 @@ __device__ __forceinline__ _Float16 rec_val<_Float16>(float v) {
 // ([r | J_host | J_target | J_rho | e], pba.h).  RecFormat<T>: what a kernel stores (S) and a record's columns per row.
 // Storage tag of the fp32 records with free target intrinsics (pba_set_optimize_intrinsics): 22 floats per row,
 // [r | J_host | J_target | J_rho | J_intr (P×8)].
+// Storage tag of the fp32 records with affine brightness (pba_set_affine_brightness): 18 floats per row,
+// [r | J_host | J_target | J_rho | J_ab_host (P×2) | J_ab_target (P×2)].
 struct ScaledF16 {};
 struct IntrF32 {};
+struct AffineF32 {};
 template <class T>
 struct RecFormat {
   using S = T;
   static constexpr int kCols = 14;
   static constexpr bool kScaled = false;
   static constexpr bool kIntr = false;
+  static constexpr bool kAffine = false;
 };
 template <>
 struct RecFormat<ScaledF16> {
@@ -151,6 +155,7 @@ struct RecFormat<ScaledF16> {
   static constexpr int kCols = 15;
   static constexpr bool kScaled = true;
   static constexpr bool kIntr = false;
+  static constexpr bool kAffine = false;
 };
 template <>
 struct RecFormat<IntrF32> {
@@ -158,7 +163,25 @@ struct RecFormat<IntrF32> {
   static constexpr int kCols = 22;
   static constexpr bool kScaled = false;
   static constexpr bool kIntr = true;
+  static constexpr bool kAffine = false;
 };
+template <>
+struct RecFormat<AffineF32> {
+  using S = float;
+  static constexpr int kCols = 18;
+  static constexpr bool kScaled = false;
+  static constexpr bool kIntr = false;
+  static constexpr bool kAffine = true;
+};
+
+// Row px of J_ab_host = [E·(I_h − b_h), E] and J_ab_target = [−E·(I_h − b_h), −1] (2 floats each at 14·P + 2·px and
+// 16·P + 2·px of the block's staged record), g = E·(I_h − b_h): two 8-B LDS writes.  A block's record is 72·P bytes and
+// the rows start 56·P + 8·px and 64·P + 8·px into it: 8-B aligned at every P, odd ones included.
+// ok = false: the zero rows of an invalid block.
+__device__ __forceinline__ void stage_affine(float* s_rec, int P, int px, float g, float E, bool ok) {
+  reinterpret_cast<float2*>(s_rec + 14 * P)[px] = ok ? make_float2(g, E) : make_float2(0.0f, 0.0f);
+  reinterpret_cast<float2*>(s_rec + 16 * P)[px] = ok ? make_float2(-g, -1.0f) : make_float2(0.0f, 0.0f);
+}
 
 // Row px of J_intr (8 floats at 14·P + 8·px of the block's staged record): two 16-B LDS writes when the row is 16-B
 // aligned — a block's record is 88·P bytes and the row starts 56·P + 32·px into it, so for even P — else four 8-B ones.
@@ -297,11 +320,14 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
     pt = stage_tile<LPB>(a, s_tb, lb, k, blk, live);
   }
   const float Ih = act ? a.host_int[(long long)pt * P + k] : 0.0f;
+  constexpr bool AFF = RecFormat<T>::kAffine;
+  Affine af = {1.0f, 0.0f, 0.0f};
+  if constexpr (AFF) af = block_affine(a, live ? blk : a.n_blocks - 1);
   __syncthreads();
   constexpr bool INTR = JAC && RecFormat<T>::kIntr;
   float ji[8];
   // dead lanes evaluate a staged block, masked by act
-  const Row row = photometric_row<PM, JAC, TileBlock, false, INTR>(a, s_tb[lb], off, Ih, nullptr, ji);
+  const Row row = photometric_row<PM, JAC, TileBlock, false, INTR, AFF>(a, s_tb[lb], off, Ih, nullptr, ji, &af);
   // per-block validity (ballot over the wave: the block's LPB lanes are an aligned bit field) and ‖r‖²
   const int ok = group_all<LPB>(act ? row.ok : 1);
   const float s = group_sum<LPB>(act ? row.r * row.r : 0.0f);
@@ -357,6 +383,7 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
       }
       stage_intr(s_rec, P, k, ji);
     }
+    if constexpr (AFF) stage_affine(s_rec, P, k, af.E * (Ih - af.bh), af.E, ok != 0);
   }
   __syncthreads();
   const int nblk = min(BPW, a.n_blocks - blk0);
@@ -433,12 +460,19 @@ constexpr int kMultiThreads = 32 * RecFormat<T>::kCols * 8 * PPL * (int)sizeof(t
 // anyway (15 halves per row: 30.7 KB of stage per workgroup, 4 per CU).
 // The 22-column records (IntrF32; the camera-table form serves their 9–16 px): 45 KB of stage per workgroup at 16 px,
 // 3 workgroups per CU, so 3 waves per SIMD is all the LDS allows and the rows keep their registers.
+// The 18-column records (AffineF32) likewise: 37 KB of stage + 6 KB of tile at 16 px, 3 workgroups per CU; their
+// 17–32 px run 128 threads (kMultiThreads) and never take the camera-table form.
+// KB4 with affine brightness: held to 168 VGPRs its rows spilled 24–128 B per lane (the table-free form takes 182–198),
+// so that camera-table form is compiled for 2 waves per SIMD.
 template <int PPL, class T>
-constexpr int kMultiWaves = RecFormat<T>::kIntr ? 3 : (RecFormat<T>::kScaled && PPL != 3 ? 5 : 6);
+constexpr int kMultiWaves =
+    RecFormat<T>::kIntr || RecFormat<T>::kAffine ? 3 : (RecFormat<T>::kScaled && PPL != 3 ? 5 : 6);
+template <int PM, int PPL, class T>
+constexpr int kMultiWavesPM = RecFormat<T>::kAffine && cam_of(PM) == CAM_KB4 ? 2 : kMultiWaves<PPL, T>;
 
 template <int PM, int MODE, class T, int PPL, bool CT = false, bool C1 = false>
 __global__ __launch_bounds__((kMultiThreads<PPL, T>))
-__attribute__((amdgpu_waves_per_eu(CT ? (kMultiWaves<PPL, T>) : 1, 8)))
+__attribute__((amdgpu_waves_per_eu(CT ? (kMultiWavesPM<PM, PPL, T>) : 1, 8)))
 void photometric_block_kernel_multi(const KernelArgs a) {
   constexpr int LPB = 8, NTH = kMultiThreads<PPL, T>, BPW = NTH / LPB;
   constexpr bool JAC = MODE == 1;
@@ -480,6 +514,9 @@ void photometric_block_kernel_multi(const KernelArgs a) {
     const int px = k + LPB * j;
     Ih[j] = live && px < P ? a.host_int[(long long)pt * P + px] : 0.0f;
   }
+  constexpr bool AFF = RecFormat<T>::kAffine;
+  Affine af = {1.0f, 0.0f, 0.0f};
+  if constexpr (AFF) af = block_affine(a, live ? blk : a.n_blocks - 1);
   __syncthreads();
   S* s_rec = stage + lb * rec_f;
   int okl = 1;
@@ -489,13 +526,17 @@ void photometric_block_kernel_multi(const KernelArgs a) {
     const bool act = live && px < P;
     constexpr bool INTR = JAC && RecFormat<T>::kIntr;
     float ji[8];
-    const Row row = photometric_row<PM, JAC, TB, C1, INTR>(a, s_tb[lb], s_pat[px < P ? px : 0], ih, s_cam, ji);  // masked by act
+    const Row row =  // masked by act
+        photometric_row<PM, JAC, TB, C1, INTR, AFF>(a, s_tb[lb], s_pat[px < P ? px : 0], ih, s_cam, ji, &af);
     okl &= act ? row.ok : 1;
     s += act ? row.r * row.r : 0.0f;
     if constexpr (JAC && RecFormat<T>::kScaled) stage_row_scaled(s_rec, lb, P, px, row, act);
     else if constexpr (JAC) stage_row<S>(s_rec, P, px, row, act);
     if constexpr (INTR) {
       if (act) stage_intr(s_rec, P, px, ji);
+    }
+    if constexpr (JAC && AFF) {
+      if (act) stage_affine(s_rec, P, px, af.E * (ih - af.bh), af.E, true);
     }
     return row.r;
   };
@@ -555,6 +596,7 @@ void photometric_block_kernel_multi(const KernelArgs a) {
         const float z[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         stage_intr(s_rec, P, px, z);
       }
+      if constexpr (AFF) stage_affine(s_rec, P, px, 0.0f, 0.0f, false);
     }
   }
   __syncthreads();
@@ -709,11 +751,15 @@ template <int PM>
 void launch_photometric(pba_engine* e, KernelArgs ka, int mode) {
   const bool h = e->record_format == PBA_RECORD_F16, hs = e->record_format == PBA_RECORD_F16_SCALED;
   const bool in = e->opt_intr;  // 22-column fp32 records (the half formats are refused with free intrinsics)
+  const bool af = e->affine;    // 18-column fp32 records (affine brightness: refused with the half formats and with `in`)
   if (e->P <= 8) {
     const int grid = (int)(((long long)e->n_blocks * 8 + kBlockThreads - 1) / kBlockThreads);
     e->last_grid = grid;
     ka.slab_wt = grid <= kSlabWtGrid;  // one wave of workgroups: write-through record stores (store_slab)
-    if (mode == 1 && in) photometric_block_kernel<PM, 8, 1, IntrF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    if (mode == 1 && af) photometric_block_kernel<PM, 8, 1, AffineF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    else if (mode == 0 && af) photometric_block_kernel<PM, 8, 0, AffineF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    else if (mode == 2 && af) photometric_block_kernel<PM, 8, 2, AffineF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
+    else if (mode == 1 && in) photometric_block_kernel<PM, 8, 1, IntrF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 0 && in) photometric_block_kernel<PM, 8, 0, IntrF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 1 && hs) photometric_block_kernel<PM, 8, 1, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
     else if (mode == 0 && hs) photometric_block_kernel<PM, 8, 0, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
@@ -746,7 +792,10 @@ void launch_photometric(pba_engine* e, KernelArgs ka, int mode) {
     }                                                                                                   \
   }
 #define PBA_LAUNCH_PPL(PPL)                                        \
-  if (mode == 1 && in) PBA_LAUNCH_ONE(PPL, 1, IntrF32)             \
+  if (mode == 1 && af) PBA_LAUNCH_ONE(PPL, 1, AffineF32)           \
+  else if (mode == 0 && af) PBA_LAUNCH_ONE(PPL, 0, AffineF32)      \
+  else if (mode == 2 && af) PBA_LAUNCH_ONE(PPL, 2, AffineF32)      \
+  else if (mode == 1 && in) PBA_LAUNCH_ONE(PPL, 1, IntrF32)        \
   else if (mode == 0 && in) PBA_LAUNCH_ONE(PPL, 0, IntrF32)        \
   else if (mode == 1 && hs) PBA_LAUNCH_ONE(PPL, 1, ScaledF16)      \
   else if (mode == 0 && hs) PBA_LAUNCH_ONE(PPL, 0, ScaledF16)      \
@@ -815,6 +864,7 @@ KernelArgs make_kernel_args(pba_engine* e, const PairRec* pairs, const double* r
   ka.host_int = e->host_int.p;
   ka.rho = rho;
   ka.u_obs = e->u_obs.p;
+  if (e->affine) ka.affine = e->affine_state.p;  // (photometric: u_obs unused, the slot is shared)
   ka.out = e->out.p;
   ka.cost = e->cost.p;
   ka.valid = e->valid.p;
@@ -853,7 +903,7 @@ int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, dou
 
 extern "C" {
 
-int pba_version(void) { return 102; }
+int pba_version(void) { return 103; }
 
 const char* pba_status_string(int s) {
   switch (s) {
@@ -899,7 +949,7 @@ int pba_destroy(pba_engine* e) {
   e->intr.release(); e->intr_d.release(); e->frame_cam.release(); e->images.release(); e->u_ref.release(); e->host_int.release(); e->point_host_d.release();
   e->block_point.release(); e->block_pair.release(); e->block_pp.release(); e->u_obs.release(); e->pair_host.release();
   e->pair_target.release(); e->block_rec.release(); e->pairs.release(); e->poses.release(); e->rho.release(); e->out.release();
-  e->cost.release(); e->valid.release();
+  e->cost.release(); e->valid.release(); e->affine_state.release();
   for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : e->chunk_ev) (void)hipEventDestroy(ev);
   if (e->res_ev) (void)hipEventDestroy(e->res_ev);
@@ -1004,6 +1054,8 @@ int pba_set_optimize_intrinsics(pba_engine* e, int32_t enable) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
   if (enable && e->record_format != PBA_RECORD_F32)
     return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics need PBA_RECORD_F32 records (J_intr has no half format)");
+  if (enable && e->affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics and affine brightness are not combined (no 26-column record)");
   if (enable && e->n_cams <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_cameras first");
   if (int rc = check_device(e)) return rc;
   const bool on = enable != 0;
@@ -1017,6 +1069,61 @@ int pba_set_optimize_intrinsics(pba_engine* e, int32_t enable) {
   e->pairs_fresh = false;  // (a photometric pair's target part is the state's)
   e->gn.prepared = false;  // the reduced camera system gains / loses its intrinsics border
   if (e->n_blocks > 0) PBA_HIP(e->out.resize((size_t)e->n_blocks * e->rec_floats()));
+  return PBA_OK;
+}
+
+// The affine state [a_0 b_0 a_1 b_1 …] at zeros (pba_set_affine_brightness, pba_set_frames*).
+static int zero_affine_state(pba_engine* e) {
+  if (e->n_frames <= 0) return PBA_OK;
+  PBA_HIP(e->affine_state.resize(2 * (size_t)e->n_frames));
+  PBA_HIP(hipMemsetAsync(e->affine_state.p, 0, sizeof(double) * 2 * (size_t)e->n_frames, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  return PBA_OK;
+}
+
+int pba_set_affine_brightness(pba_engine* e, int32_t enable) {
+  if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
+  if (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "affine brightness is photometric only");
+  if (enable && e->record_format != PBA_RECORD_F32)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "affine brightness needs PBA_RECORD_F32 records (no half format)");
+  if (enable && e->opt_intr)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "affine brightness and free intrinsics are not combined (no 26-column record)");
+  if (int rc = check_device(e)) return rc;
+  const bool on = enable != 0;
+  if (on)
+    if (int rc = zero_affine_state(e)) return rc;
+  e->affine = on;
+  e->evaluated = false;
+  e->res_fresh = false;
+  if (e->n_blocks > 0) PBA_HIP(e->out.resize((size_t)e->n_blocks * e->rec_floats()));
+  return PBA_OK;
+}
+
+static int affine_state_ready(pba_engine* e, const void* p) {
+  if (!e || !p) return fail(PBA_ERR_INVALID_ARGUMENT, "null argument");
+  if (e->n_frames <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_frames first");
+  if (!e->affine) return fail(PBA_ERR_NOT_READY, "pba_set_affine_brightness first");
+  return check_device(e);
+}
+
+int pba_set_affine_state(pba_engine* e, const double* ab) {
+  if (int rc = affine_state_ready(e, ab)) return rc;
+  PBA_HIP(hipMemcpyAsync(e->affine_state.p, ab, sizeof(double) * 2 * (size_t)e->n_frames, hipMemcpyHostToDevice, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));  // (the caller's memory is free to change on return)
+  return PBA_OK;
+}
+
+int pba_set_affine_state_device(pba_engine* e, const double* d_ab) {
+  if (int rc = affine_state_ready(e, d_ab)) return rc;
+  PBA_HIP(hipMemcpyAsync(e->affine_state.p, d_ab, sizeof(double) * 2 * (size_t)e->n_frames, hipMemcpyDeviceToDevice, e->stream));
+  return PBA_OK;
+}
+
+int pba_get_affine_state(pba_engine* e, double* ab) {
+  if (int rc = affine_state_ready(e, ab)) return rc;
+  PBA_HIP(hipMemcpyAsync(ab, e->affine_state.p, sizeof(double) * 2 * (size_t)e->n_frames, hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
   return PBA_OK;
 }
 
@@ -1125,6 +1232,8 @@ static int set_frames_impl(pba_engine* e, int32_t n_frames, const int32_t* frame
   e->n_frames = n_frames;
   e->width = width;
   e->height = height;
+  if (e->affine)  // a new set of keyframes starts at a = b = 0
+    if (int rc = zero_affine_state(e)) return rc;
   return upload_block_records(e);
 }
 
@@ -1413,6 +1522,8 @@ int pba_set_record_format(pba_engine* e, int32_t format) {
     return fail(PBA_ERR_INVALID_ARGUMENT, "fp16 records are photometric only");
   if (format != PBA_RECORD_F32 && e->opt_intr)
     return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics need PBA_RECORD_F32 records (J_intr has no half format)");
+  if (format != PBA_RECORD_F32 && e->affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "affine brightness needs PBA_RECORD_F32 records (no half format)");
   e->record_format = format;
   e->evaluated = false;
   e->res_fresh = false;

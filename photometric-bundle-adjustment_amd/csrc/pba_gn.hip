@@ -1507,6 +1507,9 @@ int ensure_prepared(pba_engine* e, bool distributed) {
   if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC && e->opt_intr && (!e->gn_solve_intr || distributed))
     return fail(PBA_ERR_INVALID_ARGUMENT,
                 "the on-device Gauss-Newton solve does not support free intrinsics on a photometric engine");
+  // the linearisation kernels evaluate the rows themselves, without (a, b): the solve would run at a = b = 0
+  if (e->affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "the on-device Gauss-Newton solve does not support affine brightness");
   if (int rc = check_device(e)) return rc;
   if (!e->gn.prepared)
     if (int rc = gn_prepare(e)) return rc;

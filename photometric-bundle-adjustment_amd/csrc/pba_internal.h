@@ -208,7 +208,10 @@ struct KernelArgs {
   const double2* u_ref;          // per point
   const float* host_int;         // P per point
   const double* rho;             // per point (state)
-  const double2* u_obs;          // per block (geometric)
+  union {                        // (one slot: the kernel-argument layout is the one every existing kernel is built for)
+    const double2* u_obs;        // per block (geometric)
+    const double* affine;        // photometric engines with pba_set_affine_brightness: the affine state
+  };                             // [a_0 b_0 a_1 b_1 …], 2 per keyframe
   float* out;                    // records
   float* res_out;                // residual-only launches: R contiguous fp32 residuals per block (pba_get_residuals)
   float* cost;                   // per block
@@ -542,6 +545,31 @@ __device__ __forceinline__ void adopt_state(const KernelArgs& a) {
   if (g < a.n_pose_d) a.adopt_poses[g] = p;
 }
 
+// Affine brightness of one block (pba_set_affine_brightness): E = exp(a_t − a_h), b_h, b_t of its host and target
+// keyframes.  a_t − a_h and the exponential in fp64 from the fp64 state, once per block (its lanes agree); floats from
+// there on.  A non-finite a makes E NaN (exp(−inf) = 0 would leave r finite), so the block is invalid.  The ids come
+// from the block record (fused state) or the block's pair (table path); blk < n_blocks.
+struct Affine {
+  float E, bh, bt;
+};
+__device__ __forceinline__ Affine block_affine(const KernelArgs& a, int blk) {
+  int h, t;
+  if (a.poses) {
+    const int4 br = a.block_rec[blk];
+    h = br.y;
+    t = br.z;
+  } else {
+    const PairRec& pr = a.pairs[a.block_pp[blk].y];
+    h = pr.host;
+    t = pr.target;
+  }
+  const double2 ah = reinterpret_cast<const double2*>(a.affine)[h];
+  const double2 at = reinterpret_cast<const double2*>(a.affine)[t];
+  const double d = at.x - ah.x;  // (±inf − ±inf and NaN stay NaN)
+  const double E = isfinite(ah.x) && isfinite(at.x) ? exp(d) : __builtin_nan("");
+  return {(float)E, (float)ah.y, (float)at.y};
+}
+
 // Photometric row k of a staged block (photometric_error.h:139-182 with the bilinear or Ceres' bicubic interpolator; the
 // Jacobian chain of pba_device.h).  Warp and projection in fp64, chain in fp32.  off = pattern offset k,
 // Ih = host intensity I_h,k.
@@ -550,9 +578,13 @@ __device__ __forceinline__ void adopt_state(const KernelArgs& a) {
 // INTR (with JAC): also ji[0..7] = ∇I · ∂π/∂k at p̃, the row of J_intr with respect to the level-0 intrinsics state of
 // the target's camera (no minus sign: r = I_t(π) − I_h).  fp32 (project_intr_jac) on the fp64 projection's 1/den;
 // KB4's θ is the fp64 projection's (pba_device.h).  Columns of parameters the model does not use are exact zeros.
-template <int PM, bool JAC, class TB = TileBlock, bool C1 = false, bool INTR = false>
+// AFF: the affine brightness residual r = (I − b_t) − E·(I_h − b_h) with the block's `af` (block_affine); at a = b = 0
+// both differences and the product are exact, so r is I − I_h bit for bit.  ∇I does not depend on (a, b): the
+// Jacobian chain is unchanged, and the caller forms the four brightness columns from E, I_h and b_h.
+template <int PM, bool JAC, class TB = TileBlock, bool C1 = false, bool INTR = false, bool AFF = false>
 __device__ __forceinline__ Row photometric_row(const KernelArgs& a, const TB& tb, float2 off, float Ih,
-                                               const CamRec* tab = nullptr, float* ji = nullptr) {
+                                               const CamRec* tab = nullptr, float* ji = nullptr,
+                                               const Affine* af = nullptr) {
   constexpr int MODEL = cam_of(PM);
   Row o;
   const auto& pp = pose_of(tb);
@@ -570,7 +602,8 @@ __device__ __forceinline__ Row photometric_row(const KernelArgs& a, const TB& tb
   double u, v;
   const double iden = project<MODEL>(cv.tk, p, u, v);
   interpolate<interp_of(PM)>(a.images + tb.img, a.umax, a.vmax, a.tiles_x, u, v, I, gx, gy);
-  o.r = I - Ih;  // photometric_error.h:179
+  if (AFF) o.r = (I - af->bt) - af->E * (Ih - af->bh);
+  else o.r = I - Ih;  // photometric_error.h:179
   o.ok = dom && isfinite(o.r);
   if (JAC) {
     // q = ∇I · ∂π/∂p̃ (1×3)
@@ -899,6 +932,8 @@ struct pba_engine {
   bool host_int_sampled = false;     // I_h,k sampled on the device (pba_set_points without intensities)
   bool opt_intr = false;             // pba_set_optimize_intrinsics: target intrinsics state + J_intr record tail
   bool gn_solve_intr = false;        // pba_gn_set_solve_intrinsics: a photometric engine's on-device solve frees them too
+  bool affine = false;               // pba_set_affine_brightness: r = (I − b_t) − E·(I_h − b_h), 18-column records
+  pba::detail::DevBuf<double> affine_state;  // its state [a_0 b_0 a_1 b_1 …] (2 per keyframe; zeros after pba_set_frames)
   pba::detail::DevBuf<float> intr_state;     // its projection constants (8 floats per camera) at the active level
   pba::detail::DevBuf<double> intr_state_d;  // and fp64 camera records (kCamD per camera)
   // photometric engines: the level-0 state as the caller set it (8 per camera); the device copy above is its image at
@@ -924,8 +959,9 @@ struct pba_engine {
   int R() const { return opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC ? P : 2; }
   // the on-device Gauss-Newton solve carries the intrinsics state as unknowns (the border of the reduced system)
   bool gn_free_intr() const { return opt_intr && (opt.residual_kind == PBA_RESIDUAL_GEOMETRIC || gn_solve_intr); }
-  // values per record: [r | J_host | J_target | J_rho] (14R), + J_intr (8R) with pba_set_optimize_intrinsics
-  int rec_floats() const { return (opt_intr ? 22 : 14) * R(); }
+  // values per record: [r | J_host | J_target | J_rho] (14R), + J_intr (8R) with pba_set_optimize_intrinsics, or
+  // + J_ab_host | J_ab_target (2R each) with pba_set_affine_brightness (the two are not combined)
+  int rec_floats() const { return (affine ? 18 : opt_intr ? 22 : 14) * R(); }
   // device bytes per record as stored: fp32 values, halves, or halves with the scale column (15R, pba.h)
   int rec_bytes() const {
     return record_format == PBA_RECORD_F16_SCALED ? 30 * R() : (record_format == PBA_RECORD_F16 ? 2 : 4) * rec_floats();

@@ -272,6 +272,8 @@ int pba_get_host_intensities(pba_engine* e, float* out) {
 // (initial cost of the coarsest level, final cost at level 0).
 int pba_solve_pyramid(pba_engine* e, const pba_solver_options* options, pba_solver_summary* summary) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
+  if (e->affine)  // refused before a level is switched, so the engine stays as it was (pba_solve refuses the same)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "the on-device Gauss-Newton solve does not support affine brightness");
   const int n = std::max(1, (int)e->pyr.size());
   pba_solver_summary acc{};
   for (int l = n - 1; l >= 0; --l) {

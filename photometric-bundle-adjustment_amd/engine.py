@@ -191,6 +191,10 @@ def lib(path: Optional[str] = None):
         "pba_gn_set_solve_intrinsics": ([vp, i32], C.c_int),
         "pba_set_intrinsics_state": ([vp, vp], C.c_int),
         "pba_get_intrinsics": ([vp, vp], C.c_int),
+        "pba_set_affine_brightness": ([vp, i32], C.c_int),
+        "pba_set_affine_state": ([vp, vp], C.c_int),
+        "pba_set_affine_state_device": ([vp, vp], C.c_int),
+        "pba_get_affine_state": ([vp, vp], C.c_int),
         "pba_gn_system_size": ([vp, C.POINTER(i32)], C.c_int),
         "pba_gn_set_rank": ([vp, i32], C.c_int),
         "pba_compute_projections": ([vp, i32, vp, vp, vp, vp, C.POINTER(OutlierThresholds), vp, vp, vp, vp], C.c_int),
@@ -368,7 +372,7 @@ class Engine:
     @property
     def record_floats(self) -> int:
         """Values per record as records() returns them (pba_record_floats): 14·R in every record format, 22·R with
-        set_optimize_intrinsics (fp32 records only)."""
+        set_optimize_intrinsics, 18·R with set_affine_brightness (fp32 records only)."""
         return self._L.pba_record_floats(self._h)
 
     @property
@@ -590,6 +594,30 @@ class Engine:
             raise ValueError("intrinsics state shape mismatch")
         self._ck(self._L.pba_set_intrinsics_state(self._h, _p(k)), "pba_set_intrinsics_state")
 
+    # -- affine brightness (a_f, b_f) per keyframe (photometric engines) --------------------------------
+    def set_affine_brightness(self, enable: bool = True):
+        """r_k = (I_t − b_t) − exp(a_t − a_h)·(I_h,k − b_h) with the affine state (set_affine_state; zeros when enabled
+        and after every set_problem); the records grow to 18·R values with J_ab_host and J_ab_target (R×2 each) as their
+        tail (split_record).  fp32 records only; not combined with set_optimize_intrinsics; the on-device solve refuses."""
+        self._ck(self._L.pba_set_affine_brightness(self._h, int(bool(enable))), "pba_set_affine_brightness")
+        self.record = self._L.pba_record_floats(self._h)
+
+    def set_affine_state(self, ab: np.ndarray):
+        """(n_frames, 2) [a_f, b_f]."""
+        ab = np.ascontiguousarray(ab, np.float64)
+        if ab.size != 2 * self.n_frames:
+            raise ValueError("affine state shape mismatch")
+        self._ck(self._L.pba_set_affine_state(self._h, _p(ab)), "pba_set_affine_state")
+
+    def set_affine_state_device(self, ab_ptr: int):
+        """The same from 2·n_frames doubles in device memory (copied on the engine stream)."""
+        self._ck(self._L.pba_set_affine_state_device(self._h, C.c_void_p(ab_ptr)), "pba_set_affine_state_device")
+
+    def get_affine_state(self) -> np.ndarray:
+        ab = np.empty((self.n_frames, 2), np.float64)
+        self._ck(self._L.pba_get_affine_state(self._h, _p(ab)), "pba_get_affine_state")
+        return ab
+
     def get_state(self):
         poses = np.empty((self.n_frames, 7), np.float64)
         rho = np.empty(self.n_points, np.float64)
@@ -739,9 +767,12 @@ def outlier_landmarks(n_points: int, obs_point, obs_frame, flags, obs_is_outlier
 
 def split_record(rec: np.ndarray, R: int):
     """(r, J_host, J_target, J_rho) views of a record array — and J_intr (n, R, 8) as a fifth when the records carry it
-    (22·R values per record: set_optimize_intrinsics)."""
+    (22·R values per record: set_optimize_intrinsics), or J_ab_host and J_ab_target (n, R, 2 each) as a fifth and sixth
+    (18·R values per record: set_affine_brightness)."""
     n = rec.shape[0]
     parts = (rec[:, :R], rec[:, R:7 * R].reshape(n, R, 6), rec[:, 7 * R:13 * R].reshape(n, R, 6), rec[:, 13 * R:14 * R])
     if rec.shape[1] == 22 * R:
         parts += (rec[:, 14 * R:22 * R].reshape(n, R, 8),)
+    elif rec.shape[1] == 18 * R:
+        parts += (rec[:, 14 * R:16 * R].reshape(n, R, 2), rec[:, 16 * R:18 * R].reshape(n, R, 2))
     return parts
