@@ -215,11 +215,11 @@ int pba_get_intrinsics(pba_engine* engine, double* intrinsics);
  * pba_set_affine_brightness: enabling sets the state to zeros, disabling restores the 14·R records.  Refused with
  * PBA_ERR_INVALID_ARGUMENT, the engine left as it was: on a geometric engine; with a half record format active (and
  * pba_set_record_format then refuses the half formats: the brightness columns have no half layout); together with
- * pba_set_optimize_intrinsics, whichever comes second (a 26-column record is not built).  While it is enabled every
- * on-device Gauss-Newton entry point (pba_gn_*, pba_solve, pba_solve_pyramid, pba_gn_step_export/import,
- * pba_solve_distributed(_comm)) returns PBA_ERR_INVALID_ARGUMENT: its linearisation evaluates the rows itself and
- * would solve with a = b = 0.  The consumer is an outer solver over the records (include/pba_ceres.h,
- * GpuPhotometricAffineCost).
+ * pba_set_optimize_intrinsics, whichever comes second (a 26-column record is not built).  While it is enabled, and
+ * unless pba_gn_set_solve_affine (below) opts in, every on-device Gauss-Newton entry point (pba_gn_*, pba_solve,
+ * pba_solve_pyramid, pba_gn_step_export/import, pba_solve_distributed(_comm)) returns PBA_ERR_INVALID_ARGUMENT instead
+ * of solving with a = b = 0.  The consumer of the brightness columns is an outer solver over the records
+ * (include/pba_ceres.h, GpuPhotometricAffineCost).
  * pba_set_affine_state / _device (host / device memory) and pba_get_affine_state move the 2·n_frames doubles;
  * PBA_ERR_NOT_READY before pba_set_frames or without pba_set_affine_brightness.  pba_set_frames* resets the state to
  * zeros.  pba_evaluate_state(s)_device keep taking poses and inverse distances only: the affine state is the engine's,
@@ -228,6 +228,40 @@ int pba_set_affine_brightness(pba_engine* engine, int32_t enable);
 int pba_set_affine_state(pba_engine* engine, const double* ab);
 int pba_set_affine_state_device(pba_engine* engine, const double* d_ab);
 int pba_get_affine_state(pba_engine* engine, double* ab);
+/* Photometric engines with pba_set_affine_brightness: enable = 1 makes the single-GPU on-device solve
+ * (pba_gn_linearize/step/candidate_cost/accept, pba_gn_get_reduced_system/get_step, pba_solve, pba_solve_pyramid) run
+ * with the residual above at the engine's affine state, which those calls hold constant — Ceres'
+ * SetParameterBlockConstant on the (a, b) blocks (problem.h:306): poses and inverse distances are solved, the state
+ * is left bit for bit as it was.  ∇I_t does not depend on (a, b), so J_host, J_target and J_rho are the plain solve's
+ * and at the zero state every result is the plain engine's bit for bit.  (a, b) are shared by the pyramid levels.
+ * A linearisation or candidate formed before pba_set_affine_state* is stale afterwards, as after pba_set_state.
+ * Default 0: those entry points refuse as before.  PBA_ERR_INVALID_ARGUMENT, nothing changed, on an engine without
+ * pba_set_affine_brightness; disabling affine brightness clears the switch.  The multi-GPU entry points
+ * (pba_gn_step_export/import, pba_solve_distributed(_comm)) refuse either way. */
+int pba_gn_set_solve_affine(pba_engine* engine, int32_t enable);
+/* The brightness solve at fixed poses and inverse distances (photometric engines with pba_set_affine_brightness; no
+ * opt-in: the entry points are new).  Exactly a Ceres solve of the (a, b) blocks with the pose and inverse-distance
+ * blocks constant (Problem::SetParameterBlockConstant, problem.h:306), with the pose solve's rules: per-block Huber
+ * through the Corrector (corrector.cc:42-110, ρ'' ≤ 0: J̃ = √ρ' J, r̃ = √ρ' r), cost Σ ½ρ(‖r‖²), damping
+ * (H + λ·clamp(diag H, 1e-6, 1e32)) δ = −g (levenberg_marquardt_strategy.cc), model decrease ½(λ δᵀDδ − gᵀδ), identity
+ * rows for the keyframes of pba_set_fixed_affine_frames (default none) and for keyframes without a valid block (δ = 0
+ * there).  The system is 2·n_frames square, unknowns [a_0 b_0 a_1 b_1 …]; every sum is fp64 in a fixed order, so results
+ * are bitwise reproducible.  pba_affine_get_system: the undamped system dense (row-major) and g, constant rows as
+ * identity / zero — testing and inspection.  pba_affine_step: solver_status ≠ 0 and no candidate when the damped system
+ * is not positive definite.  pba_affine_accept: affine state ← candidate.  pba_solve_affine: Ceres' trust-region loop
+ * (trust_region_minimizer.cc:67-136) driven from the host, norms over the free (a, b); fills the summary (the device
+ * phase times stay 0) and the trajectory pba_solver_iterations serves.  Alternated with pba_solve under
+ * pba_gn_set_solve_affine the two give a photometric BA with brightness on the device.
+ * PBA_ERR_INVALID_ARGUMENT on a geometric engine or without pba_set_affine_brightness, and for a fixed keyframe out of
+ * range (nothing changed); PBA_ERR_NOT_READY for a call before the one it follows (step before linearize, …). */
+int pba_set_fixed_affine_frames(pba_engine* engine, int32_t n, const int32_t* frames);
+int pba_affine_linearize(pba_engine* engine, double* cost);  /* cost may be NULL */
+int pba_affine_system_size(pba_engine* engine, int32_t* n);  /* 2·n_frames */
+int pba_affine_get_system(pba_engine* engine, double* H_dense, double* g);
+int pba_affine_step(pba_engine* engine, double lambda, double* model_decrease, int32_t* solver_status);
+int pba_affine_get_step(pba_engine* engine, double* d_ab);
+int pba_affine_candidate_cost(pba_engine* engine, double* cost);
+int pba_affine_accept(pba_engine* engine);
 /* Image interpolator of the photometric residual (and of the device-sampled I_h,k): PBA_INTERP_BILINEAR (default,
  * the north star's) or PBA_INTERP_BICUBIC — Ceres' BiCubicInterpolator over Grid2D<uint8_t, 1>
  * (cubic_interpolation.h:252-344, edge clamp :403-414), the interpolator of PhotometricError<8>
@@ -359,6 +393,8 @@ typedef struct pba_iteration_summary {
 /* copies min(capacity, entries) entries of the last pba_solve / pba_solve_distributed(_comm) into out (may be NULL with
  * capacity 0) and the number of entries into count; replaces reading Solver::Summary::iterations (map_utils.h:384-392) */
 int pba_solver_iterations(const pba_engine* engine, int32_t capacity, pba_iteration_summary* out, int32_t* count);
+/* the brightness solve's LM loop (see pba_affine_linearize above) */
+int pba_solve_affine(pba_engine* engine, const pba_solver_options* options, pba_solver_summary* summary);
 
 /* constant parameter blocks (Problem::SetParameterBlockConstant, map_utils.h:334-336) */
 int pba_set_fixed_frames(pba_engine* engine, int32_t n, const int32_t* frames);

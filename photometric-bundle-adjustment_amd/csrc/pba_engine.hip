@@ -886,9 +886,10 @@ void launch_pairs(pba_engine* e, const double* poses, PairRec* pairs) {
 }
 
 int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, double* wg_red, int* n_slots,
-                     const double* poses, const float* intr_t, const double* intr_t_d) {
+                     const double* poses, const float* intr_t, const double* intr_t_d, const double* affine) {
   KernelArgs ka = make_kernel_args(e, pairs, rho);
   ka.poses = poses;
+  if (affine && e->affine) ka.affine = affine;
   if (intr_t) ka.intr_t = intr_t;
   if (intr_t_d) ka.intr_t_d = intr_t_d;
   ka.wg_red = wg_red;
@@ -903,7 +904,7 @@ int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, dou
 
 extern "C" {
 
-int pba_version(void) { return 103; }
+int pba_version(void) { return 104; }
 
 const char* pba_status_string(int s) {
   switch (s) {
@@ -1094,6 +1095,7 @@ int pba_set_affine_brightness(pba_engine* e, int32_t enable) {
   if (on)
     if (int rc = zero_affine_state(e)) return rc;
   e->affine = on;
+  if (!on) e->gn_solve_affine = false;  // (the switch belongs to the affine engine: asked for again when it comes back)
   e->evaluated = false;
   e->res_fresh = false;
   if (e->n_blocks > 0) PBA_HIP(e->out.resize((size_t)e->n_blocks * e->rec_floats()));
@@ -1133,6 +1135,14 @@ int pba_gn_set_solve_intrinsics(pba_engine* e, int32_t enable) {
   const bool on = enable != 0;
   if (on != e->gn_solve_intr) e->gn.prepared = false;  // the reduced camera system gains / loses its intrinsics border
   e->gn_solve_intr = on;
+  return PBA_OK;
+}
+
+int pba_gn_set_solve_affine(pba_engine* e, int32_t enable) {
+  if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
+  if (enable && !e->affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "pba_gn_set_solve_affine needs pba_set_affine_brightness");
+  e->gn_solve_affine = enable != 0;  // (the GN structure does not depend on it: the same reduced camera system)
   return PBA_OK;
 }
 
@@ -1229,6 +1239,9 @@ static int set_frames_impl(pba_engine* e, int32_t n_frames, const int32_t* frame
   e->frame_cam_h.assign(frame_cam, frame_cam + n_frames);
   e->pairs_fresh = false;
   e->gn.prepared = false;  // the GN structure (frame count, the pairs' camera records) is re-analysed on next use
+  e->aff.planned = false;
+  e->aff.fixed_h.clear();
+  e->aff.linearized = e->aff.have_step = false;
   e->n_frames = n_frames;
   e->width = width;
   e->height = height;
@@ -1358,6 +1371,8 @@ int pba_set_blocks(pba_engine* e, int32_t n_blocks, const int32_t* block_point, 
   e->pair_host_h = std::move(ph);
   e->pair_target_h = std::move(pt);
   e->gn.prepared = false;
+  e->aff.planned = false;
+  e->aff.linearized = e->aff.have_step = false;
   return upload_block_records(e);
 }
 

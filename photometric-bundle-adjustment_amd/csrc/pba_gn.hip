@@ -1507,9 +1507,14 @@ int ensure_prepared(pba_engine* e, bool distributed) {
   if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC && e->opt_intr && (!e->gn_solve_intr || distributed))
     return fail(PBA_ERR_INVALID_ARGUMENT,
                 "the on-device Gauss-Newton solve does not support free intrinsics on a photometric engine");
-  // the linearisation kernels evaluate the rows themselves, without (a, b): the solve would run at a = b = 0
-  if (e->affine)
+  // without pba_gn_set_solve_affine the caller has not asked for a solve that holds (a, b) constant: refused, as
+  // before that switch existed; the multi-GPU entry points refuse either way
+  if (e->affine && (!e->gn_solve_affine || distributed))
     return fail(PBA_ERR_INVALID_ARGUMENT, "the on-device Gauss-Newton solve does not support affine brightness");
+  // the 14-column lineariser of the test build (its A/B hook) has no affine form: it would solve at a = b = 0
+  // (the hook's name stays out of the message: the product library carries no hook names)
+  if (e->affine && e->gn.lin_legacy)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "the 14-column lineariser has no affine brightness form");
   if (int rc = check_device(e)) return rc;
   if (!e->gn.prepared)
     if (int rc = gn_prepare(e)) return rc;

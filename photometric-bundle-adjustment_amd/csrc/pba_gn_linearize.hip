@@ -348,7 +348,11 @@ __host__ __device__ constexpr int upper8(int r, int c) { return r * 8 - r * (r -
 // NT: threads per workgroup (NT / 8 blocks per chunk).  Measured at 8 px: 512 threads (64-block chunks: the phases,
 // partial slots, assembly contributions and decision slots per chunk spread over twice the blocks) 71.1 → 76.6 µs for
 // the linearisation against 12.1 → 10.9 for the assembly — the 8-wave barriers cost more than the halved chunk work.
-template <int MODEL, int PPL, int NT>
+// AFF (pba_gn_set_solve_affine): the rows' residual is r = (I − b_t) − E·(I_h − b_h) at the engine's affine state, held
+// constant — block_affine once per block in the first memory round (the pair-table branch: host and target from the
+// block's pair) and photometric_row<…, AFF>, the record path's formula and bits.  ∇I does not depend on (a, b): the
+// Jacobian columns, the products and everything downstream are the same code.
+template <int MODEL, int PPL, int NT, bool AFF = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PPL == 1 ? 8 : PBA_LINADJ_WAVES, 8)))
 void linearize_adj_kernel(const KernelArgs a, const LinArgs g) {
   constexpr int LPB = 8, BW = 64 / LPB, NW = NT / 64;
@@ -393,6 +397,12 @@ void linearize_adj_kernel(const KernelArgs a, const LinArgs g) {
   const int blk = lr.x, gpos = lr.w, lt = (int)((unsigned)lr.z >> 24);
   TileBlock* s_tb = reinterpret_cast<TileBlock*>(arena[wave]);
   float* sX = reinterpret_cast<float*>(arena[wave] + kRowsOff);  // the wave's 64 rows
+  // the block's pair is in the linearise record: block_affine goes pair → keyframes' state without the block → pair load
+  // (a dead slot repeats slot 0: a live block's pair); PPL > 1 parks E, b_h, b_t in LDS across the pass loop, read back
+  // per pass like the tile (three registers fewer across the row: the 17–32-px pinhole forms spilled them)
+  __shared__ float s_af[AFF && PPL > 1 ? NT / LPB : 1][3];
+  Affine af = {1.0f, 0.0f, 0.0f};
+  if constexpr (AFF) af = block_affine(a, blk, lr.z & 0xffffff);
   // lane l: 4×4 block β — tiles (0,0), (0,1), (1,1) of xᵀx, and β = 3 repeating (0,1) unused — operand columns
   // ca / cb, product (pr_, pc_)
   const int beta = (lane >> 2) & 3, i4 = lane & 3, kq = lane >> 4;
@@ -433,7 +443,8 @@ void linearize_adj_kernel(const KernelArgs a, const LinArgs g) {
     row.tv = Vec3{row.r, row.r, row.r};
     row.tw = row.tv;
 #else
-    const Row row = photometric_row<MODEL, true>(a, s_tb[wb], off, Ih);  // (hv, hw unused: not formed)
+    const Row row =  // (hv, hw unused: not formed)
+        photometric_row<MODEL, true, TileBlock, false, false, AFF>(a, s_tb[wb], off, Ih, nullptr, nullptr, &af);
 #endif
     save_rt();
     ok = group_all<LPB>(act ? row.ok : 1);
@@ -460,6 +471,13 @@ void linearize_adj_kernel(const KernelArgs a, const LinArgs g) {
     stage_tile_pp<LPB>(a, s_tb, wb, k, make_int2(lr.y, lr.z & 0xffffff));
 #pragma unroll
     for (int j = 0; j < PPL; ++j) asm volatile("" ::"v"(Ih[j]));
+    if constexpr (AFF) {
+      if (k == 0) {
+        s_af[lb][0] = af.E;
+        s_af[lb][1] = af.bh;
+        s_af[lb][2] = af.bt;
+      }
+    }
     __syncthreads();
     save_rt();
 #pragma unroll
@@ -482,7 +500,10 @@ void linearize_adj_kernel(const KernelArgs a, const LinArgs g) {
       row.tv = Vec3{row.r, row.r, row.r};
       row.tw = row.tv;
 #else
-      const Row row = photometric_row<MODEL, true>(a, s_tb[wb], s_pat[act ? px : 0], ih);
+      Affine afl = af;
+      if constexpr (AFF) afl = Affine{s_af[lb][0], s_af[lb][1], s_af[lb][2]};
+      const Row row = photometric_row<MODEL, true, TileBlock, false, false, AFF>(a, s_tb[wb], s_pat[act ? px : 0], ih,
+                                                                                 nullptr, nullptr, &afl);
 #endif
       const bool use = act && row.ok;
       okl &= act ? row.ok : 1;
@@ -674,6 +695,14 @@ template <int KIND, int MODEL>  // photometric: MODEL = camera model + 4 · inte
 void launch_linearize(pba_engine* e, const KernelArgs& ka, const LinArgs& la) {
   const int grid = la.n_chunks;
   if constexpr (KIND == PBA_RESIDUAL_PHOTOMETRIC) {
+    if (e->affine) {  // the solve at the engine's affine state (ensure_prepared: pba_gn_set_solve_affine is on)
+      switch (e->gn.ppl) {
+        case 1: linearize_adj_kernel<MODEL, 1, kBlockThreads, true><<<grid, kBlockThreads, 0, e->stream>>>(ka, la); return;
+        case 2: linearize_adj_kernel<MODEL, 2, kBlockThreads, true><<<grid, kBlockThreads, 0, e->stream>>>(ka, la); return;
+        case 3: linearize_adj_kernel<MODEL, 3, kBlockThreads, true><<<grid, kBlockThreads, 0, e->stream>>>(ka, la); return;
+        default: linearize_adj_kernel<MODEL, 4, kBlockThreads, true><<<grid, kBlockThreads, 0, e->stream>>>(ka, la); return;
+      }
+    }
     switch (e->gn.ppl) {  // 9…32 px: 8 lanes per block, ⌈P/8⌉ rows per lane
       case 1: break;
       case 2: linearize_adj_kernel<MODEL, 2, kBlockThreads><<<grid, kBlockThreads, 0, e->stream>>>(ka, la); return;

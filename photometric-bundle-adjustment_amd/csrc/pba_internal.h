@@ -552,14 +552,16 @@ __device__ __forceinline__ void adopt_state(const KernelArgs& a) {
 struct Affine {
   float E, bh, bt;
 };
-__device__ __forceinline__ Affine block_affine(const KernelArgs& a, int blk) {
+// pair ≥ 0: the block's pair when the caller already holds it (the lineariser's record): one dependent load fewer on
+// the table path.
+__device__ __forceinline__ Affine block_affine(const KernelArgs& a, int blk, int pair = -1) {
   int h, t;
-  if (a.poses) {
+  if (pair < 0 && a.poses) {
     const int4 br = a.block_rec[blk];
     h = br.y;
     t = br.z;
   } else {
-    const PairRec& pr = a.pairs[a.block_pp[blk].y];
+    const PairRec& pr = a.pairs[pair >= 0 ? pair : a.block_pp[blk].y];
     h = pr.host;
     t = pr.target;
   }
@@ -900,7 +902,27 @@ struct LevelData {
 #include <atomic>
 #include <memory>
 
+// The brightness solve at fixed poses and inverse distances (pba_affine.hip; photometric engines with
+// pba_set_affine_brightness): its plan (pba_affine_plan.h) on the device, the per-block moment records, the
+// (a, b) normal equations as a 2×2-block skyline, their factor and the candidate affine state.
+struct AffineSolve {
+  bool planned = false;            // cleared when the frames or blocks change
+  std::vector<uint8_t> fixed_h;    // pba_set_fixed_affine_frames (empty: none)
+  int n_sky = 0, max_row = 0;
+  std::vector<int> first_h, row_h;
+  pba::detail::DevBuf<int> pair_ptr, pair_blocks, frame_ptr, frame_pairs, first, row, off_ptr, off_pairs;
+  pba::detail::DevBuf<uint8_t> fixed;
+  pba::detail::DevBuf<double> rec;       // 8 per block: w, E, Σc², Σc, Σcr, Σr, cost, valid
+  pba::detail::DevBuf<double> pair_rec;  // 16 per pair: H_hh (3), H_tt (3), H_ht (4), g_h (2), g_t (2)
+  pba::detail::DevBuf<double> S0, g;     // undamped system (4 per skyline block, row-major 2×2) and gradient
+  pba::detail::DevBuf<double> L, x;      // the damped system, factored in place; the step
+  pba::detail::DevBuf<double> ab_new;    // candidate affine state
+  pba::detail::DevBuf<double> red, out;  // cost partials; {status, model decrease, step max-norm, δᵀδ}
+  bool linearized = false, have_step = false;
+};
+
 struct pba_engine {
+  AffineSolve aff;
   pba_options opt{};
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -934,6 +956,7 @@ struct pba_engine {
   bool gn_solve_intr = false;        // pba_gn_set_solve_intrinsics: a photometric engine's on-device solve frees them too
   bool affine = false;               // pba_set_affine_brightness: r = (I − b_t) − E·(I_h − b_h), 18-column records
   pba::detail::DevBuf<double> affine_state;  // its state [a_0 b_0 a_1 b_1 …] (2 per keyframe; zeros after pba_set_frames)
+  bool gn_solve_affine = false;      // pba_gn_set_solve_affine: the on-device solve runs at that state, held constant
   pba::detail::DevBuf<float> intr_state;     // its projection constants (8 floats per camera) at the active level
   pba::detail::DevBuf<double> intr_state_d;  // and fp64 camera records (kCamD per camera)
   // photometric engines: the level-0 state as the caller set it (8 per camera); the device copy above is its image at
@@ -988,7 +1011,7 @@ void launch_pairs(pba_engine* e, const double* poses, PairRec* pairs);
 // intr_t / intr_t_d (optional): the target projection's intrinsics (a candidate's free intrinsics).
 int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, double* wg_red = nullptr,
                      int* n_slots = nullptr, const double* poses = nullptr, const float* intr_t = nullptr,
-                     const double* intr_t_d = nullptr);
+                     const double* intr_t_d = nullptr, const double* affine = nullptr);  // affine: a candidate affine state
 
 // Collectives of the multi-GPU loop (pba_comm.hip): Σ over the ranks in place, enqueued on stream.
 int comm_allreduce(pba_comm* c, double* buf, long long count, hipStream_t stream);

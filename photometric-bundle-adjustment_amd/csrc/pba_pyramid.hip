@@ -272,8 +272,12 @@ int pba_get_host_intensities(pba_engine* e, float* out) {
 // (initial cost of the coarsest level, final cost at level 0).
 int pba_solve_pyramid(pba_engine* e, const pba_solver_options* options, pba_solver_summary* summary) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
-  if (e->affine)  // refused before a level is switched, so the engine stays as it was (pba_solve refuses the same)
+  // refused before a level is switched, so the engine stays as it was (pba_solve refuses the same); with
+  // pba_gn_set_solve_affine the levels solve at the engine's affine state, which they share
+  if (e->affine && !e->gn_solve_affine)
     return fail(PBA_ERR_INVALID_ARGUMENT, "the on-device Gauss-Newton solve does not support affine brightness");
+  if (e->affine && e->gn.lin_legacy)  // (the test build's A/B hook: ensure_prepared would refuse after the level switch)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "the 14-column lineariser has no affine brightness form");
   const int n = std::max(1, (int)e->pyr.size());
   pba_solver_summary acc{};
   for (int l = n - 1; l >= 0; --l) {

@@ -195,6 +195,16 @@ def lib(path: Optional[str] = None):
         "pba_set_affine_state": ([vp, vp], C.c_int),
         "pba_set_affine_state_device": ([vp, vp], C.c_int),
         "pba_get_affine_state": ([vp, vp], C.c_int),
+        "pba_gn_set_solve_affine": ([vp, i32], C.c_int),
+        "pba_set_fixed_affine_frames": ([vp, i32, vp], C.c_int),
+        "pba_affine_linearize": ([vp, C.POINTER(C.c_double)], C.c_int),
+        "pba_affine_system_size": ([vp, C.POINTER(i32)], C.c_int),
+        "pba_affine_get_system": ([vp, vp, vp], C.c_int),
+        "pba_affine_step": ([vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i32)], C.c_int),
+        "pba_affine_get_step": ([vp, vp], C.c_int),
+        "pba_affine_candidate_cost": ([vp, C.POINTER(C.c_double)], C.c_int),
+        "pba_affine_accept": ([vp], C.c_int),
+        "pba_solve_affine": ([vp, C.POINTER(SolverOptions), C.POINTER(SolverSummary)], C.c_int),
         "pba_gn_system_size": ([vp, C.POINTER(i32)], C.c_int),
         "pba_gn_set_rank": ([vp, i32], C.c_int),
         "pba_compute_projections": ([vp, i32, vp, vp, vp, vp, C.POINTER(OutlierThresholds), vp, vp, vp, vp], C.c_int),
@@ -598,9 +608,65 @@ class Engine:
     def set_affine_brightness(self, enable: bool = True):
         """r_k = (I_t − b_t) − exp(a_t − a_h)·(I_h,k − b_h) with the affine state (set_affine_state; zeros when enabled
         and after every set_problem); the records grow to 18·R values with J_ab_host and J_ab_target (R×2 each) as their
-        tail (split_record).  fp32 records only; not combined with set_optimize_intrinsics; the on-device solve refuses."""
+        tail (split_record).  fp32 records only; not combined with set_optimize_intrinsics; the on-device solve refuses
+        unless gn_set_solve_affine opts in."""
         self._ck(self._L.pba_set_affine_brightness(self._h, int(bool(enable))), "pba_set_affine_brightness")
         self.record = self._L.pba_record_floats(self._h)
+
+    def gn_set_solve_affine(self, enable: bool = True):
+        """Photometric engines with set_affine_brightness: the single-GPU on-device Gauss-Newton (gn_linearize / gn_step /
+        gn_candidate_cost / gn_accept, solve, solve_pyramid) solves poses and inverse distances at the engine's affine
+        state, which it holds constant.  Off by default (those entry points refuse); refused without
+        set_affine_brightness; the multi-GPU entry points refuse either way."""
+        self._ck(self._L.pba_gn_set_solve_affine(self._h, int(bool(enable))), "pba_gn_set_solve_affine")
+
+    # -- the brightness solve at fixed poses and inverse distances (pba_affine.hip) -------------------
+    def set_fixed_affine_frames(self, frames):
+        f = np.ascontiguousarray(frames, np.int32)
+        self._ck(self._L.pba_set_fixed_affine_frames(self._h, f.shape[0], _p(f) if f.size else None),
+                 "pba_set_fixed_affine_frames")
+
+    def affine_linearize(self) -> float:
+        c = C.c_double()
+        self._ck(self._L.pba_affine_linearize(self._h, C.byref(c)), "pba_affine_linearize")
+        return c.value
+
+    def affine_system_size(self) -> int:
+        n = C.c_int32()
+        self._ck(self._L.pba_affine_system_size(self._h, C.byref(n)), "pba_affine_system_size")
+        return n.value
+
+    def affine_system(self):
+        """(H (2·n_frames square, undamped, constant keyframes as identity rows), g)"""
+        n = self.affine_system_size()
+        H, g = np.empty((n, n), np.float64), np.empty(n, np.float64)
+        self._ck(self._L.pba_affine_get_system(self._h, _p(H), _p(g)), "pba_affine_get_system")
+        return H, g
+
+    def affine_step(self, lam: float):
+        m, st = C.c_double(), C.c_int32()
+        self._ck(self._L.pba_affine_step(self._h, lam, C.byref(m), C.byref(st)), "pba_affine_step")
+        return m.value, st.value
+
+    def affine_last_step(self) -> np.ndarray:
+        d = np.empty((self.n_frames, 2), np.float64)
+        self._ck(self._L.pba_affine_get_step(self._h, _p(d)), "pba_affine_get_step")
+        return d
+
+    def affine_candidate_cost(self) -> float:
+        c = C.c_double()
+        self._ck(self._L.pba_affine_candidate_cost(self._h, C.byref(c)), "pba_affine_candidate_cost")
+        return c.value
+
+    def affine_accept(self):
+        self._ck(self._L.pba_affine_accept(self._h), "pba_affine_accept")
+
+    def solve_affine(self, **options) -> dict:
+        """pba_solve_affine; options as solver_options()."""
+        o = solver_options(**options)
+        s = SolverSummary()
+        self._ck(self._L.pba_solve_affine(self._h, C.byref(o), C.byref(s)), "pba_solve_affine")
+        return s.as_dict()
 
     def set_affine_state(self, ab: np.ndarray):
         """(n_frames, 2) [a_f, b_f]."""
