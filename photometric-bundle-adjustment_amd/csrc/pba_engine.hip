@@ -1,19 +1,7 @@
-// pba_engine.hip — HIP kernels + C ABI (include/pba.h) of the photometric BA residual/Jacobian engine.
-//
-// Replaces, for every residual block of a problem at once, the reference's per-block CPU evaluation:
-//   ProgramEvaluator::Evaluate ParallelFor (program_evaluator.h:187-258) →
-//   ResidualBlock::Evaluate (residual_block.cc:69-158) → AutoDiffCostFunction<Functor,…> →
-//   BundleAdjustmentReprojectionCostFunctor (reprojection.h:83-112) / PhotometricError (photometric_error.h:139-182)
-//
-// Photometric evaluation is ONE launch (photometric_block_kernel): one lane per (block, pattern pixel), a wave =
-// 64/LPB blocks.  Each block's lanes form its relative pose T_th = T_w_t⁻¹ T_w_h in fp64 from the state poses in
-// the tile prologue (fused state, pba_internal.h:stage_tile) — or copy it from the pair table (pair_kernel /
-// state_kernel: the geometric kernels and the Gauss-Newton path) — with u_ref and ρ into LDS; image taps are
-// gathered from the target keyframe's tiled u8 image, the Jacobian chain stays in registers, per-block ‖r‖² and
-// validity come from wave shuffles, and the workgroup's records leave as one contiguous slab.
+// pba_engine.hip — the C ABI (include/pba.h) of the photometric BA residual/Jacobian engine and the engine's state:
+// problem upload (image tiling, pair table, state) and read-back.  The evaluation itself — the block kernels and their
+// launches — is pba_evaluate.hip; the record layout both sides read is pba_record.h.
 #include <hip/hip_runtime.h>
-
-#include <type_traits>
 
 #include <algorithm>
 #include <chrono>
@@ -24,6 +12,7 @@
 #include <vector>
 
 #include "pba_internal.h"
+#include "pba_record.h"
 
 using namespace pba;
 using namespace pba::detail;
@@ -121,760 +110,10 @@ __global__ void tile_images_kernel(const uint8_t* __restrict__ src, uint8_t* __r
   reinterpret_cast<uint4*>(dst)[i] = row.v;
 }
 
-// A record value in the engine's format.  fp16 saturates at ±65504 (the half range) instead of rounding to ±inf: at
-// full resolution a strong edge's rotation Jacobian ∇I·∂π/∂p·[b]× reaches ~1e5 intensity units per radian (measured
-// up to 9.0e4 on the C5-style problem), so those entries are clamped (pba.h, PBA_RECORD_F16).
-template <class T>
-__device__ __forceinline__ T rec_val(float v) { return (T)v; }
-template <>
-__device__ __forceinline__ _Float16 rec_val<_Float16>(float v) {
-  // (fmed3 would map NaN to −65504: a NaN stays NaN)
-  return (_Float16)(isnan(v) ? v : __builtin_amdgcn_fmed3f(v, -65504.0f, 65504.0f));
-}
-
-// Storage tag of PBA_RECORD_F16_SCALED: halves with one power-of-two scale per pixel row, 15 halves per row
-// ([r | J_host | J_target | J_rho | e], pba.h).  RecFormat<T>: what a kernel stores (S) and a record's columns per row.
-// Storage tag of the fp32 records with free target intrinsics (pba_set_optimize_intrinsics): 22 floats per row,
-// [r | J_host | J_target | J_rho | J_intr (P×8)].
-// Storage tag of the fp32 records with affine brightness (pba_set_affine_brightness): 18 floats per row,
-// [r | J_host | J_target | J_rho | J_ab_host (P×2) | J_ab_target (P×2)].
-struct ScaledF16 {};
-struct IntrF32 {};
-struct AffineF32 {};
-template <class T>
-struct RecFormat {
-  using S = T;
-  static constexpr int kCols = 14;
-  static constexpr bool kScaled = false;
-  static constexpr bool kIntr = false;
-  static constexpr bool kAffine = false;
-};
-template <>
-struct RecFormat<ScaledF16> {
-  using S = _Float16;
-  static constexpr int kCols = 15;
-  static constexpr bool kScaled = true;
-  static constexpr bool kIntr = false;
-  static constexpr bool kAffine = false;
-};
-template <>
-struct RecFormat<IntrF32> {
-  using S = float;
-  static constexpr int kCols = 22;
-  static constexpr bool kScaled = false;
-  static constexpr bool kIntr = true;
-  static constexpr bool kAffine = false;
-};
-template <>
-struct RecFormat<AffineF32> {
-  using S = float;
-  static constexpr int kCols = 18;
-  static constexpr bool kScaled = false;
-  static constexpr bool kIntr = false;
-  static constexpr bool kAffine = true;
-};
-
-// Row px of J_ab_host = [E·(I_h − b_h), E] and J_ab_target = [−E·(I_h − b_h), −1] (2 floats each at 14·P + 2·px and
-// 16·P + 2·px of the block's staged record), g = E·(I_h − b_h): two 8-B LDS writes.  A block's record is 72·P bytes and
-// the rows start 56·P + 8·px and 64·P + 8·px into it: 8-B aligned at every P, odd ones included.
-// ok = false: the zero rows of an invalid block.
-__device__ __forceinline__ void stage_affine(float* s_rec, int P, int px, float g, float E, bool ok) {
-  reinterpret_cast<float2*>(s_rec + 14 * P)[px] = ok ? make_float2(g, E) : make_float2(0.0f, 0.0f);
-  reinterpret_cast<float2*>(s_rec + 16 * P)[px] = ok ? make_float2(-g, -1.0f) : make_float2(0.0f, 0.0f);
-}
-
-// Row px of J_intr (8 floats at 14·P + 8·px of the block's staged record): two 16-B LDS writes when the row is 16-B
-// aligned — a block's record is 88·P bytes and the row starts 56·P + 32·px into it, so for even P — else four 8-B ones.
-__device__ __forceinline__ void stage_intr(float* s_rec, int P, int px, const float (&ji)[8]) {
-  float* d = s_rec + 14 * P + 8 * px;
-  if ((P & 1) == 0) {
-    reinterpret_cast<f32x4*>(d)[0] = f32x4{ji[0], ji[1], ji[2], ji[3]};
-    reinterpret_cast<f32x4*>(d)[1] = f32x4{ji[4], ji[5], ji[6], ji[7]};
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) reinterpret_cast<float2*>(d)[q] = make_float2(ji[2 * q], ji[2 * q + 1]);
-  }
-}
-
-// Store a workgroup's contiguous record slab (LDS → global): 16-B non-temporal stores when the slab is 16-B
-// aligned, 4-B or 2-B stores otherwise (odd patterns in fp16).
-// wt (wave-uniform, KernelArgs::slab_wt): non-temporal write-through stores (`nt sc1`) — for launches of at most one
-// wave of workgroups (a 1/8 shard of C4: 8.29 → 8.07-8.15 µs, nothing left dirty in L2 for the kernel's end), never for
-// a full C4 launch (44.9 → 46.2 µs), DESIGN.md §3.
-template <class T, int NTH = kBlockThreads>
-__device__ __forceinline__ void store_slab(const unsigned char* src, unsigned char* dst, int bytes, int wt = 0) {
-  constexpr int kBlockThreads = NTH;  // the workgroup's threads share the slab
-  if ((((uintptr_t)dst | (unsigned)bytes) & 15) == 0) {
-    // non-temporal 16-B stores (write-through sc1 stores measured 49 → 71 µs for this kernel; per-lane stores
-    // straight from registers, without the LDS slab, 49 → 104 µs: DESIGN.md §3)
-    const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
-    f32x4* d4 = reinterpret_cast<f32x4*>(dst);
-    if (wt) {
-      for (int i = threadIdx.x; i < (bytes >> 4); i += kBlockThreads)
-        asm volatile("global_store_dwordx4 %0, %1, off nt sc1" ::"v"(d4 + i), "v"(s4[i]) : "memory");
-    } else {
-      for (int i = threadIdx.x; i < (bytes >> 4); i += kBlockThreads) __builtin_nontemporal_store(s4[i], d4 + i);
-    }
-  } else if (sizeof(T) == 4 || (((uintptr_t)dst | (unsigned)bytes) & 3) == 0) {
-    const float* s1 = reinterpret_cast<const float*>(src);
-    float* d1 = reinterpret_cast<float*>(dst);
-#pragma unroll 1
-    for (int i = threadIdx.x; i < (bytes >> 2); i += kBlockThreads) __builtin_nontemporal_store(s1[i], d1 + i);
-  } else {
-    const _Float16* s1 = reinterpret_cast<const _Float16*>(src);
-    _Float16* d1 = reinterpret_cast<_Float16*>(dst);
-#pragma unroll 1
-    for (int i = threadIdx.x; i < (bytes >> 1); i += kBlockThreads) d1[i] = s1[i];
-  }
-}
-
-typedef float rec_f2 __attribute__((ext_vector_type(2)));
-typedef _Float16 rec_h2 __attribute__((ext_vector_type(2)));
-
-// Row px of a half record into its LDS stage: c = {r, J_rho}, 3 × J_host pairs, 3 × J_target pairs.  The 6-value rows
-// as 4-byte LDS writes where they are 4-byte aligned (LDS issue is what the 21-px kernel waits on: SQ_WAIT_INST_LDS
-// ≈ 0.26 of wave time): 3 per row when `even` (the J_host row starts on a 4-byte boundary), else 1 + 2 + 1 with the
-// inner pairs re-packed.
-__device__ __forceinline__ void stage_halves(_Float16* s_rec, int P, int px, const rec_h2 (&c)[7], bool even) {
-  _Float16* h = s_rec + P + 6 * px;
-  _Float16* t = s_rec + 7 * P + 6 * px;
-  s_rec[px] = c[0].x;
-  s_rec[13 * P + px] = c[0].y;
-  if (even) {
-    rec_h2* h4 = reinterpret_cast<rec_h2*>(h);
-    rec_h2* t4 = reinterpret_cast<rec_h2*>(t);
-    h4[0] = c[1]; h4[1] = c[2]; h4[2] = c[3];
-    t4[0] = c[4]; t4[1] = c[5]; t4[2] = c[6];
-  } else {
-    rec_h2* h4 = reinterpret_cast<rec_h2*>(h + 1);
-    rec_h2* t4 = reinterpret_cast<rec_h2*>(t + 1);
-    h[0] = c[1].x; h4[0] = (rec_h2){c[1].y, c[2].x}; h4[1] = (rec_h2){c[2].y, c[3].x}; h[5] = c[3].y;
-    t[0] = c[4].x; t4[0] = (rec_h2){c[4].y, c[5].x}; t4[1] = (rec_h2){c[5].y, c[6].x}; t[5] = c[6].y;
-  }
-}
-
-// Row px of a PBA_RECORD_F16_SCALED record (pba.h), by the lane that evaluated it: with m the largest magnitude of the
-// row's 13 Jacobian values, e = 1 for m < 65520 (every value rounds to a finite half: the row is stored as
-// PBA_RECORD_F16 stores it), else e = 2^(⌊log₂ m⌋ − 14) ≤ 2¹⁵, which puts the scaled maximum into [16384, 32768).  The
-// multiplication by 1/e is exact, so the one rounding is the half conversion.  Beyond 65504·2¹⁵ the scaled values
-// saturate at ±65504.  The residual is not scaled.  s_rec is block lb's record in the 4-byte aligned stage (15·P halves per
-// block: an odd P puts every other block on a 2-byte boundary).
-__device__ __forceinline__ void stage_row_scaled(_Float16* s_rec, int lb, int P, int px, const Row& row, bool act) {
-  const float j[13] = {row.jr, row.hv.x, row.hv.y, row.hv.z, row.hw.x, row.hw.y, row.hw.z,
-                       row.tv.x, row.tv.y, row.tv.z, row.tw.x, row.tw.y, row.tw.z};
-  float m = 0.0f;  // (a NaN drops out of the max and stays NaN in the record)
-#pragma unroll
-  for (int q = 0; q < 13; ++q) m = fmaxf(m, fabsf(j[q]));
-  int ex = 0;  // e = 2^ex
-  if (m >= 65520.0f) ex = min((int)((__float_as_uint(m) >> 23) & 0xffu) - (127 + 14), 15);  // (m = +inf: the cap)
-  const float inv = __uint_as_float((unsigned)(127 - ex) << 23);
-  // the residual saturates as PBA_RECORD_F16's does (|r| ≤ 255 for 8-bit images)
-  const float r = isnan(row.r) ? row.r : __builtin_amdgcn_fmed3f(row.r, -65504.0f, 65504.0f);
-  rec_h2 c[7];
-  c[0] = __builtin_convertvector((rec_f2){r, j[0] * inv}, rec_h2);
-#pragma unroll
-  for (int q = 1; q < 7; ++q) c[q] = __builtin_convertvector((rec_f2){j[2 * q - 1] * inv, j[2 * q] * inv}, rec_h2);
-  if (ex == 15) {  // the largest scale: a value beyond the format's range rounded to ±inf and saturates
-    auto sat = [](_Float16 h) -> _Float16 {
-      return __builtin_isinf(h) ? (h > (_Float16)0 ? (_Float16)65504.0f : (_Float16)-65504.0f) : h;
-    };
-    c[0].y = sat(c[0].y);
-#pragma unroll
-    for (int q = 1; q < 7; ++q) c[q] = (rec_h2){sat(c[q].x), sat(c[q].y)};
-  }
-  if (act) {
-    stage_halves(s_rec, P, px, c, ((lb + 1) & P & 1) == 0);  // J_host row at half (15·lb + 1)·P + 6·px of the stage
-    reinterpret_cast<unsigned short*>(s_rec)[14 * P + px] = (unsigned short)((15 + ex) << 10);  // 2^ex as a half
-  }
-}
-
-// PM = camera model + 4 · interpolator; T = float, _Float16, ScaledF16 or IntrF32 (RecFormat)
-template <int PM, int LPB, int MODE, class T>
-__global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const KernelArgs a) {
-  constexpr int BPW = kBlockThreads / LPB;  // blocks per workgroup
-  constexpr bool JAC = MODE == 1;
-  using S = typename RecFormat<T>::S;  // the stored type
-  constexpr int kCols = RecFormat<T>::kCols;
-  constexpr int kStageBytes = JAC ? BPW * kCols * LPB * (int)sizeof(S) : 0;
-  constexpr int kTileBytes = BPW * (int)sizeof(TileBlock);
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kStageBytes > kTileBytes ? kStageBytes : kTileBytes];
-  TileBlock* s_tb = reinterpret_cast<TileBlock*>(lds);
-  const int P = a.P;
-  const int rec_f = kCols * P;
-  const int blk0 = logical_tile() * BPW;
-  const int lb = threadIdx.x / LPB;
-  const int k = threadIdx.x % LPB;
-  const int blk = blk0 + lb;
-  const bool live = blk < a.n_blocks;  // a block's LPB lanes agree
-  const bool act = live && k < P;
-  S* out = reinterpret_cast<S*>(a.out);  // records in the engine's format (fp32, or halves: PBA_RECORD_F16 / _SCALED)
-
-  const float2 off = pattern_at<LPB>(a, k);
-  adopt_state(a);
-  int pt;
-  if (LPB == 8 && a.poses) {  // fused state: the workgroup-cooperative prologue (BPW = 32)
-    static_assert(kBlockThreads == 256, "stage_tile_wg: 4 waves, 32 blocks");
-    pt = a.block_rec[live ? blk : a.n_blocks - 1].x;
-    stage_tile_wg(a, s_tb, blk0);
-  } else {
-    pt = stage_tile<LPB>(a, s_tb, lb, k, blk, live);
-  }
-  const float Ih = act ? a.host_int[(long long)pt * P + k] : 0.0f;
-  constexpr bool AFF = RecFormat<T>::kAffine;
-  Affine af = {1.0f, 0.0f, 0.0f};
-  if constexpr (AFF) af = block_affine(a, live ? blk : a.n_blocks - 1);
-  __syncthreads();
-  constexpr bool INTR = JAC && RecFormat<T>::kIntr;
-  float ji[8];
-  // dead lanes evaluate a staged block, masked by act
-  const Row row = photometric_row<PM, JAC, TileBlock, false, INTR, AFF>(a, s_tb[lb], off, Ih, nullptr, ji, &af);
-  // per-block validity (ballot over the wave: the block's LPB lanes are an aligned bit field) and ‖r‖²
-  const int ok = group_all<LPB>(act ? row.ok : 1);
-  const float s = group_sum<LPB>(act ? row.r * row.r : 0.0f);
-  const float bc = ok ? huber_cost(s, a.huber) : 0.0f;
-  if (live && k == 0) {
-    a.valid[blk] = (uint8_t)ok;
-    a.cost[blk] = bc;
-  }
-  if (MODE == 2) {
-    if (a.wg_red) {
-      const bool one = live && k == 0;
-      wg_reduce2(one ? (double)bc : 0.0, one && ok ? 1.0 : 0.0, a.wg_red + 2 * logical_tile());
-    }
-    return;
-  }
-  if (!JAC) {
-    if (act) {
-      out[(long long)blk * rec_f + k] = rec_val<S>(ok ? row.r : 0.0f);
-      if (a.res_out) a.res_out[(long long)blk * P + k] = ok ? row.r : 0.0f;  // contiguous: one D2H copy for Ceres
-    }
-    return;
-  }
-  __syncthreads();  // every lane has read its tile block: the record stage may overwrite it
-  S* stage = reinterpret_cast<S*>(lds);
-  // stage the record row of pixel k: r | J_host row | J_target row | J_rho  (zeros for invalid blocks)
-  if constexpr (RecFormat<T>::kScaled) {  // … | e, the row's scale
-    S* s_rec = stage + lb * rec_f;
-    stage_row_scaled(s_rec, lb, P, k, row, act && ok);
-    if (act && !ok) {
-      s_rec[k] = s_rec[13 * P + k] = s_rec[14 * P + k] = (S)0.0f;
-      for (int j = 0; j < 6; ++j) s_rec[P + 6 * k + j] = s_rec[7 * P + 6 * k + j] = (S)0.0f;
-    }
-  } else if (act) {
-    S* s_rec = stage + lb * rec_f;
-    S* h = s_rec + P + 6 * k;
-    S* t = s_rec + 7 * P + 6 * k;
-    if (ok) {
-      s_rec[k] = rec_val<S>(row.r);
-      h[0] = rec_val<S>(row.hv.x); h[1] = rec_val<S>(row.hv.y); h[2] = rec_val<S>(row.hv.z);
-      h[3] = rec_val<S>(row.hw.x); h[4] = rec_val<S>(row.hw.y); h[5] = rec_val<S>(row.hw.z);
-      t[0] = rec_val<S>(row.tv.x); t[1] = rec_val<S>(row.tv.y); t[2] = rec_val<S>(row.tv.z);
-      t[3] = rec_val<S>(row.tw.x); t[4] = rec_val<S>(row.tw.y); t[5] = rec_val<S>(row.tw.z);
-      s_rec[13 * P + k] = rec_val<S>(row.jr);
-    } else {
-      s_rec[k] = (S)0.0f;
-      for (int j = 0; j < 6; ++j) h[j] = t[j] = (S)0.0f;
-      s_rec[13 * P + k] = (S)0.0f;
-    }
-    if constexpr (INTR) {
-      if (!ok) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ji[j] = 0.0f;
-      }
-      stage_intr(s_rec, P, k, ji);
-    }
-    if constexpr (AFF) stage_affine(s_rec, P, k, af.E * (Ih - af.bh), af.E, ok != 0);
-  }
-  __syncthreads();
-  const int nblk = min(BPW, a.n_blocks - blk0);
-  if (nblk <= 0) return;
-  store_slab<S>(lds, reinterpret_cast<unsigned char*>(out + (long long)blk0 * rec_f), nblk * rec_f * (int)sizeof(S),
-                a.slab_wt);
-}
-
-// Row px of a block's staged record (r | J_host row | J_target row | J_rho; T = float or _Float16), written by the lane
-// that evaluated it when act.  Every lane of the wave calls it (the fp16 form's saturation test is a ballot).
-template <class T>
-__device__ __forceinline__ void stage_row(T* s_rec, int P, int px, const Row& row, bool act) {
-  if constexpr (std::is_same<T, _Float16>::value) {
-    // fp16 records: the 14 values in 7 packed round-to-nearest conversions (v_cvt_pk_f16_f32) instead of a
-    // NaN-preserving clamp + conversion each; a value beyond the half range rounds to ±inf there, which rec_val
-    // saturates to ±65504 — applied afterwards, only when some lane of the wave has one (a ballot)
-    typedef rec_f2 f2;
-    typedef rec_h2 h2;
-    const float v[14] = {row.r, row.jr, row.hv.x, row.hv.y, row.hv.z, row.hw.x, row.hw.y, row.hw.z,
-                         row.tv.x, row.tv.y, row.tv.z, row.tw.x, row.tw.y, row.tw.z};
-    h2 c[7];
-    // a value rounds to ±inf in half precision iff |v| ≥ 65520: one max over the 14 magnitudes (v_max3 with abs
-    // modifiers; a NaN drops out of the max and stays NaN) instead of a class test per converted half
-    float m = 0.0f;
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-      c[q] = __builtin_convertvector((f2){v[2 * q], v[2 * q + 1]}, h2);
-      m = fmaxf(m, fmaxf(fabsf(v[2 * q]), fabsf(v[2 * q + 1])));
-    }
-    const bool big = m >= 65520.0f;
-    if (__ballot(act && big) != 0) {
-      auto sat = [](_Float16 h) -> _Float16 {
-        return __builtin_isinf(h) ? (h > (_Float16)0 ? (_Float16)65504.0f : (_Float16)-65504.0f) : h;
-      };
-#pragma unroll
-      for (int q = 0; q < 7; ++q) c[q] = (h2){sat(c[q].x), sat(c[q].y)};
-    }
-    // (14·P halves per block: the J_host row starts on a 4-byte boundary for even P)
-    if (act) stage_halves(s_rec, P, px, c, (P & 1) == 0);
-  } else if (act) {  // record row px: r | J_host row | J_target row | J_rho
-    T* h = s_rec + P + 6 * px;
-    T* t = s_rec + 7 * P + 6 * px;
-    s_rec[px] = rec_val<T>(row.r);
-    h[0] = rec_val<T>(row.hv.x); h[1] = rec_val<T>(row.hv.y); h[2] = rec_val<T>(row.hv.z);
-    h[3] = rec_val<T>(row.hw.x); h[4] = rec_val<T>(row.hw.y); h[5] = rec_val<T>(row.hw.z);
-    t[0] = rec_val<T>(row.tv.x); t[1] = rec_val<T>(row.tv.y); t[2] = rec_val<T>(row.tv.z);
-    t[3] = rec_val<T>(row.tw.x); t[4] = rec_val<T>(row.tw.y); t[5] = rec_val<T>(row.tw.z);
-    s_rec[13 * P + px] = rec_val<T>(row.jr);
-  }
-}
-
-// Patterns of 9…32 pixels (the 21-px pattern of config C5): still 8 lanes per block, each lane evaluating pixels
-// k, k+8, … (PPL of them), so a wave carries 8 blocks and the per-block prologue (pair record, point) is paid once
-// per 8 blocks — one lane per pixel (32 lanes per block) ran the 21-px C4 shard at 181 µs per launch with a third
-// of its lanes idle and the prologue amortised over 2 blocks per wave.  Rows go to the record stage as they are
-// produced (stage and tile in separate LDS regions); an invalid block's record is zeroed once its validity is known
-// (the same lanes rewrite their own rows: LDS operations of one wave stay in order).  256 threads per workgroup,
-// 128 when the fp32 stage of 32 blocks would not fit the 64 KiB of static LDS.
-__host__ __device__ constexpr int multi_stage_bytes(int bpw, int P, int tsize, int cols = 14) {
-  return (bpw * cols * P * tsize + 15) & ~15;
-}
-
-template <int PPL, class T>
-constexpr int kMultiThreads = 32 * RecFormat<T>::kCols * 8 * PPL * (int)sizeof(typename RecFormat<T>::S) +
-                                          32 * (int)sizeof(TileBlock) > 60 * 1024 ? 128 : 256;
-
-// CT: the camera-table form (fused state, ≤ kCamTab cameras, 256 threads): compact 192-B tile blocks plus one LDS
-// CamRec per camera instead of 352-B tile blocks carrying both cameras (the 21-px fp16 launch: 30.1 → 25.6 KB of LDS
-// per workgroup, 5 → 6 workgroups per CU, which its 78 VGPRs also allow).
-// C1 (with CT, one camera): the rows take the camera constants from scalar loads of the engine's camera record instead
-// of the LDS table (no per-row LDS reads of them, no VGPRs).
-// kMultiWaves: the waves per SIMD the camera-table form is compiled for.  6, except the scaled-half records of 9–16 and
-// 25–32 px: held to 80 VGPRs those spilled 8–28 B per lane, and six workgroups are out of reach of the 25–32-px stage
-// anyway (15 halves per row: 30.7 KB of stage per workgroup, 4 per CU).
-// The 22-column records (IntrF32; the camera-table form serves their 9–16 px): 45 KB of stage per workgroup at 16 px,
-// 3 workgroups per CU, so 3 waves per SIMD is all the LDS allows and the rows keep their registers.
-// The 18-column records (AffineF32) likewise: 37 KB of stage + 6 KB of tile at 16 px, 3 workgroups per CU; their
-// 17–32 px run 128 threads (kMultiThreads) and never take the camera-table form.
-// KB4 with affine brightness: held to 168 VGPRs its rows spilled 24–128 B per lane (the table-free form takes 182–198),
-// so that camera-table form is compiled for 2 waves per SIMD.
-template <int PPL, class T>
-constexpr int kMultiWaves =
-    RecFormat<T>::kIntr || RecFormat<T>::kAffine ? 3 : (RecFormat<T>::kScaled && PPL != 3 ? 5 : 6);
-template <int PM, int PPL, class T>
-constexpr int kMultiWavesPM = RecFormat<T>::kAffine && cam_of(PM) == CAM_KB4 ? 2 : kMultiWaves<PPL, T>;
-
-template <int PM, int MODE, class T, int PPL, bool CT = false, bool C1 = false>
-__global__ __launch_bounds__((kMultiThreads<PPL, T>))
-__attribute__((amdgpu_waves_per_eu(CT ? (kMultiWavesPM<PM, PPL, T>) : 1, 8)))
-void photometric_block_kernel_multi(const KernelArgs a) {
-  constexpr int LPB = 8, NTH = kMultiThreads<PPL, T>, BPW = NTH / LPB;
-  constexpr bool JAC = MODE == 1;
-  static_assert(!CT || NTH == 256, "camera table: the workgroup-cooperative prologue");
-  using TB = typename std::conditional<CT, TileBlockC, TileBlock>::type;
-  // dynamic LDS sized for the actual P (multi_stage_bytes): the 21-px fp16 stage is 18.4 KB instead of 21 KB for
-  // 24 px, which lets a fifth workgroup onto the CU (LDS is what bounds this kernel's occupancy)
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  __shared__ float2 s_pat[LPB * PPL];
-  __shared__ CamRec s_cam[CT ? kCamTab : 1];
-  using S = typename RecFormat<T>::S;  // the stored type
-  constexpr int kCols = RecFormat<T>::kCols;
-  const int P = a.P;
-  S* stage = reinterpret_cast<S*>(lds);
-  TB* s_tb = reinterpret_cast<TB*>(lds + (JAC ? multi_stage_bytes(BPW, P, (int)sizeof(S), kCols) : 0));
-  const int rec_f = kCols * P;
-  const int blk0 = logical_tile() * BPW;
-  const int lb = threadIdx.x / LPB;
-  const int k = threadIdx.x % LPB;
-  const int blk = blk0 + lb;
-  const bool live = blk < a.n_blocks;  // a block's LPB lanes agree
-  S* out = reinterpret_cast<S*>(a.out);
-
-  if ((int)threadIdx.x < LPB * PPL) s_pat[threadIdx.x] = pattern_at<LPB * PPL>(a, threadIdx.x);
-  adopt_state(a);
-  int pt;
-  if constexpr (CT) {
-    pt = a.block_rec[live ? blk : a.n_blocks - 1].x;
-    stage_tile_wg_ct(a, s_tb, s_cam, a.n_cams, blk0);
-  } else if (NTH == 256 && a.poses) {  // fused state: the workgroup-cooperative prologue (BPW = 32)
-    pt = a.block_rec[live ? blk : a.n_blocks - 1].x;
-    stage_tile_wg(a, s_tb, blk0);
-  } else {
-    pt = stage_tile<LPB>(a, s_tb, lb, k, blk, live);
-  }
-  float Ih[PPL];
-#pragma unroll
-  for (int j = 0; j < PPL; ++j) {
-    const int px = k + LPB * j;
-    Ih[j] = live && px < P ? a.host_int[(long long)pt * P + px] : 0.0f;
-  }
-  constexpr bool AFF = RecFormat<T>::kAffine;
-  Affine af = {1.0f, 0.0f, 0.0f};
-  if constexpr (AFF) af = block_affine(a, live ? blk : a.n_blocks - 1);
-  __syncthreads();
-  S* s_rec = stage + lb * rec_f;
-  int okl = 1;
-  float s = 0.0f, rr[PPL];
-  auto pixel = [&](int j, float ih) {
-    const int px = k + LPB * j;
-    const bool act = live && px < P;
-    constexpr bool INTR = JAC && RecFormat<T>::kIntr;
-    float ji[8];
-    const Row row =  // masked by act
-        photometric_row<PM, JAC, TB, C1, INTR, AFF>(a, s_tb[lb], s_pat[px < P ? px : 0], ih, s_cam, ji, &af);
-    okl &= act ? row.ok : 1;
-    s += act ? row.r * row.r : 0.0f;
-    if constexpr (JAC && RecFormat<T>::kScaled) stage_row_scaled(s_rec, lb, P, px, row, act);
-    else if constexpr (JAC) stage_row<S>(s_rec, P, px, row, act);
-    if constexpr (INTR) {
-      if (act) stage_intr(s_rec, P, px, ji);
-    }
-    if constexpr (JAC && AFF) {
-      if (act) stage_affine(s_rec, P, px, af.E * (ih - af.bh), af.E, true);
-    }
-    return row.r;
-  };
-  if constexpr (JAC) {
-    // one pixel at a time (no unrolling: an unrolled loop interleaves the PPL rows' evaluations and needed 122 VGPRs,
-    // 4 waves per SIMD); the pixel's I_h,k selected from the registers by a compare chain
-#pragma unroll 1
-    for (int j = 0; j < PPL; ++j) {
-      float ih = Ih[0];
-#pragma unroll
-      for (int q = 1; q < PPL; ++q) ih = j == q ? Ih[q] : ih;
-      // the tile block (pair record, cameras, point: ~70 registers) is read from LDS again by every pixel instead of
-      // being hoisted out of the loop and kept live across it
-      asm volatile("" ::: "memory");
-      pixel(j, ih);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) rr[j] = pixel(j, Ih[j]);
-  }
-  // per-block validity (ballot over the wave: the block's LPB lanes are an aligned bit field) and ‖r‖²
-  const int ok = group_all<LPB>(okl);
-  s = group_sum<LPB>(s);
-  const float bc = ok ? huber_cost(s, a.huber) : 0.0f;
-  if (live && k == 0) {
-    a.valid[blk] = (uint8_t)ok;
-    a.cost[blk] = bc;
-  }
-  if (MODE == 2) {
-    if (a.wg_red) {
-      const bool one = live && k == 0;
-      wg_reduce2(one ? (double)bc : 0.0, one && ok ? 1.0 : 0.0, a.wg_red + 2 * logical_tile());
-    }
-    return;
-  }
-  if (!JAC) {
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) {
-      const int px = k + LPB * j;
-      if (live && px < P) {
-        out[(long long)blk * rec_f + px] = rec_val<S>(ok ? rr[j] : 0.0f);
-        if (a.res_out) a.res_out[(long long)blk * P + px] = ok ? rr[j] : 0.0f;
-      }
-    }
-    return;
-  }
-  if (live && !ok) {  // an invalid block leaves a zero record (Ceres' Evaluate returning false)
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) {
-      const int px = k + LPB * j;
-      if (px >= P) continue;
-      s_rec[px] = (S)0.0f;
-      s_rec[13 * P + px] = (S)0.0f;
-      for (int q = 0; q < 6; ++q) s_rec[P + 6 * px + q] = s_rec[7 * P + 6 * px + q] = (S)0.0f;
-      if constexpr (kCols == 15) s_rec[14 * P + px] = (S)0.0f;
-      if constexpr (RecFormat<T>::kIntr) {
-        const float z[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        stage_intr(s_rec, P, px, z);
-      }
-      if constexpr (AFF) stage_affine(s_rec, P, px, 0.0f, 0.0f, false);
-    }
-  }
-  __syncthreads();
-  const int nblk = min(BPW, a.n_blocks - blk0);
-  if (nblk <= 0) return;
-  store_slab<S, NTH>(lds, reinterpret_cast<unsigned char*>(out + (long long)blk0 * rec_f), nblk * rec_f * (int)sizeof(S));
-}
-
-// ------------------------------------------------------------------------------------------------
-// Geometric block kernel (reprojection.h:105-108): lane = block, record 28 floats = 7 float4 stores, or with the
-// target-intrinsics Jacobian (INTR, pba_set_optimize_intrinsics) 44 floats = 11 float4 stores
-// ------------------------------------------------------------------------------------------------
-template <int MODEL, bool JAC, bool INTR>
-__global__ __launch_bounds__(kBlockThreads) void geometric_block_kernel(const KernelArgs a) {
-  constexpr int NR = INTR ? 44 : 28;
-  const int blk_ = logical_tile() * kBlockThreads + threadIdx.x;
-  const bool live = blk_ < a.n_blocks;
-  if (!live && !a.wg_red) return;  // (with wg_red every thread reaches the workgroup reduction)
-  const int blk = live ? blk_ : a.n_blocks - 1;
-  const int pt = a.block_point[blk];
-  const PairRec& pp = a.pairs[a.block_pair[blk]];
-  // the host camera unprojects with the constant intrinsics (the functor's captured ref_intrinsics, reprojection.h:
-  // 93-98), the target camera projects with the intrinsics parameter block (sIntr_c2)
-  const double* khd = a.intr_d + kCamD * pp.host_cam;
-  const double* ktd = a.intr_t_d + kCamD * pp.target_cam;
-  const double2 ur = a.u_ref[pt];
-  const double2 uo = a.u_obs[blk];
-  const double rho = a.rho[pt];
-  const double irho = rcp_nr(rho);
-  // p = T_w_t⁻¹ · T_w_h · (b / ρ) in fp64
-  const Vec3d b = unproject<MODEL>(khd + kCamHk, ur.x, ur.y);
-  const Vec3d ph = {b.x * irho, b.y * irho, b.z * irho};
-  const Vec3d Rp = mat_mul(pp.R, ph);
-  const Vec3d p = {Rp.x + pp.t[0], Rp.y + pp.t[1], Rp.z + pp.t[2]};
-  double u, v;
-  const double iden = project<MODEL>(ktd, p, u, v);
-  const float r0 = (float)(uo.x - u), r1 = (float)(uo.y - v);
-  f32x4* rec = reinterpret_cast<f32x4*>(a.out + (long long)blk * NR);
-  float J[NR];
-  J[0] = r0;
-  J[1] = r1;
-  bool ok = isfinite(r0) && isfinite(r1);
-  if (JAC) {
-    const Vec3 pf = to_f(p), phf = to_f(ph);
-    const Vec3 tf = {(float)pp.t[0], (float)pp.t[1], (float)pp.t[2]};
-    const float irf = (float)irho;
-    Vec3 du, dv;
-    project_jac<MODEL>(a.intr_t + 8 * pp.target_cam, pf, (float)iden, du, dv);
-    if (INTR) {  // ∂r/∂k = −∂π/∂k (2×8, row-major) after J_rho
-      double ku[8], kv[8];
-      project_intr_jac<MODEL>(ktd, p, iden, ku, kv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        J[28 + j] = (float)-ku[j];
-        J[36 + j] = (float)-kv[j];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const Vec3 d = i == 0 ? du : dv;
-      const Vec3 g = {-d.x, -d.y, -d.z};  // ∂r/∂p = −∂π/∂p
-      const Vec3 gR = row_mul(g, pp.R);
-      const Vec3 wh = cross(phf, gR);
-      const Vec3 wt = cross(g, pf);
-      float* jh = J + 2 + 6 * i;
-      float* jt = J + 14 + 6 * i;
-      jh[0] = gR.x; jh[1] = gR.y; jh[2] = gR.z; jh[3] = wh.x; jh[4] = wh.y; jh[5] = wh.z;
-      jt[0] = -g.x; jt[1] = -g.y; jt[2] = -g.z; jt[3] = wt.x; jt[4] = wt.y; jt[5] = wt.z;
-      J[26 + i] = dot(g, tf) * irf;  // = ∂π/∂p·R b/ρ² without the cancellation (∂π/∂p·p = 0), pba_internal.h
-    }
-#pragma unroll
-    for (int i = 2; i < NR; ++i) ok = ok && isfinite(J[i]);
-  }
-  const float bc = ok ? huber_cost(r0 * r0 + r1 * r1, a.huber) : 0.0f;
-  if (a.wg_red) {
-    wg_reduce2(live ? (double)bc : 0.0, live && ok ? 1.0 : 0.0, a.wg_red + 2 * logical_tile());
-    if (!live) return;
-  }
-  a.valid[blk] = (uint8_t)ok;
-  a.cost[blk] = bc;
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < NR; ++i) J[i] = 0.0f;
-  }
-  if (JAC) {
-#pragma unroll
-    for (int i = 0; i < NR / 4; ++i)
-      __builtin_nontemporal_store(f32x4{J[4 * i], J[4 * i + 1], J[4 * i + 2], J[4 * i + 3]}, rec + i);
-  } else {
-    reinterpret_cast<float2*>(rec)[0] = make_float2(J[0], J[1]);
-    if (a.res_out) reinterpret_cast<float2*>(a.res_out)[blk] = make_float2(J[0], J[1]);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Record decode (pba_decode_records_device): half records → 14·P floats per block.  A workgroup takes kDecodeBlocks
-// blocks: their contiguous half records into LDS by 16-B loads (32 records start on a 64-B boundary of the engine's
-// record array), then 4 consecutive output values per lane as one 16-B store.  cols = 14 (PBA_RECORD_F16: a plain
-// conversion) or 15 (PBA_RECORD_F16_SCALED: a Jacobian entry of pixel row k times the row's scale e[k], exact).
-// ------------------------------------------------------------------------------------------------
-constexpr int kDecodeBlocks = 32;
-
-__global__ __launch_bounds__(kBlockThreads) void decode_records_kernel(const _Float16* __restrict__ in,
-                                                                        float* __restrict__ out, int n_blocks, int P,
-                                                                        int cols) {
-  __shared__ __attribute__((aligned(16))) _Float16 s[kDecodeBlocks * 15 * PBA_MAX_PATTERN];
-  const int b0 = blockIdx.x * kDecodeBlocks;
-  const int nb = min(kDecodeBlocks, n_blocks - b0);
-  const int rec_i = cols * P, rec_o = 14 * P;
-  const int n_in = nb * rec_i, n_out = nb * rec_o;
-  const _Float16* src = in + (long long)b0 * rec_i;
-  {
-    const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
-    f32x4* d4 = reinterpret_cast<f32x4*>(s);
-    for (int i = threadIdx.x; i < (n_in >> 3); i += kBlockThreads) d4[i] = __builtin_nontemporal_load(s4 + i);
-    for (int i = (n_in & ~7) + threadIdx.x; i < n_in; i += kBlockThreads) s[i] = src[i];
-  }
-  __syncthreads();
-  auto value = [&](int o) -> float {
-    const int b = o / rec_o, c = o - b * rec_o;
-    const _Float16* r = s + b * rec_i;
-    float v = (float)r[c];
-    if (cols == 15 && c >= P) {  // column c of [r | J_host (P×6) | J_target (P×6) | J_rho (P)] belongs to pixel row:
-      const int row = c < 13 * P ? ((c - P) % (6 * P)) / 6 : c - 13 * P;
-      v *= (float)r[14 * P + row];
-    }
-    return v;
-  };
-  float* dst = out + (long long)b0 * rec_o;
-  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-    f32x4* d4 = reinterpret_cast<f32x4*>(dst);
-    for (int i = threadIdx.x; i < (n_out >> 2); i += kBlockThreads)
-      __builtin_nontemporal_store(f32x4{value(4 * i), value(4 * i + 1), value(4 * i + 2), value(4 * i + 3)}, d4 + i);
-    for (int i = (n_out & ~3) + threadIdx.x; i < n_out; i += kBlockThreads) dst[i] = value(i);
-  } else {
-    for (int i = threadIdx.x; i < n_out; i += kBlockThreads) dst[i] = value(i);
-  }
-}
-
-template <int MODEL>
-void launch_geometric(pba_engine* e, const KernelArgs& ka, int mode) {
-  const int grid = (e->n_blocks + kBlockThreads - 1) / kBlockThreads;
-  e->last_grid = grid;
-  if (mode == 1 && e->opt_intr) geometric_block_kernel<MODEL, true, true><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-  else if (mode == 1) geometric_block_kernel<MODEL, true, false><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-  else if (e->opt_intr) geometric_block_kernel<MODEL, false, true><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-  else geometric_block_kernel<MODEL, false, false><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-}
-
-// PM = camera model + 4 · interpolator (pba_device.h)
-template <int PM>
-void launch_photometric(pba_engine* e, KernelArgs ka, int mode) {
-  const bool h = e->record_format == PBA_RECORD_F16, hs = e->record_format == PBA_RECORD_F16_SCALED;
-  const bool in = e->opt_intr;  // 22-column fp32 records (the half formats are refused with free intrinsics)
-  const bool af = e->affine;    // 18-column fp32 records (affine brightness: refused with the half formats and with `in`)
-  if (e->P <= 8) {
-    const int grid = (int)(((long long)e->n_blocks * 8 + kBlockThreads - 1) / kBlockThreads);
-    e->last_grid = grid;
-    ka.slab_wt = grid <= kSlabWtGrid;  // one wave of workgroups: write-through record stores (store_slab)
-    if (mode == 1 && af) photometric_block_kernel<PM, 8, 1, AffineF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 0 && af) photometric_block_kernel<PM, 8, 0, AffineF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 2 && af) photometric_block_kernel<PM, 8, 2, AffineF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 1 && in) photometric_block_kernel<PM, 8, 1, IntrF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 0 && in) photometric_block_kernel<PM, 8, 0, IntrF32><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 1 && hs) photometric_block_kernel<PM, 8, 1, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 0 && hs) photometric_block_kernel<PM, 8, 0, ScaledF16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 1 && h) photometric_block_kernel<PM, 8, 1, _Float16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 1) photometric_block_kernel<PM, 8, 1, float><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 0 && h) photometric_block_kernel<PM, 8, 0, _Float16><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else if (mode == 0) photometric_block_kernel<PM, 8, 0, float><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    else photometric_block_kernel<PM, 8, 2, float><<<grid, kBlockThreads, 0, e->stream>>>(ka);
-    return;
-  }
-  // 9…32 pixels: 8 lanes per block, ⌈P/8⌉ pixels per lane
-  // the camera-table form for record launches at a fused state with few cameras (the C5 configuration)
-  const bool ct = mode == 1 && ka.poses != nullptr && ka.n_cams <= kCamTab;
-#define PBA_LAUNCH_ONE(PPL, M, TT)                                                                      \
-  {                                                                                                     \
-    constexpr int nth = kMultiThreads<PPL, TT>;                                                         \
-    const int grid = (int)(((long long)e->n_blocks * 8 + nth - 1) / nth);                              \
-    e->last_grid = grid;                                                                                \
-    const size_t stage = M == 1 ? multi_stage_bytes(nth / 8, e->P, (int)sizeof(RecFormat<TT>::S),      \
-                                                    RecFormat<TT>::kCols) : 0;                         \
-    if (M == 1 && nth == 256 && ct && ka.n_cams == 1) {                                                 \
-      photometric_block_kernel_multi<PM, M, TT, PPL, (M == 1 && nth == 256), (M == 1 && nth == 256)>    \
-          <<<grid, nth, stage + (size_t)(nth / 8) * sizeof(TileBlockC), e->stream>>>(ka);              \
-    } else if (M == 1 && nth == 256 && ct) {                                                            \
-      photometric_block_kernel_multi<PM, M, TT, PPL, (M == 1 && nth == 256)>                            \
-          <<<grid, nth, stage + (size_t)(nth / 8) * sizeof(TileBlockC), e->stream>>>(ka);              \
-    } else {                                                                                            \
-      photometric_block_kernel_multi<PM, M, TT, PPL>                                                    \
-          <<<grid, nth, stage + (size_t)(nth / 8) * sizeof(TileBlock), e->stream>>>(ka);               \
-    }                                                                                                   \
-  }
-#define PBA_LAUNCH_PPL(PPL)                                        \
-  if (mode == 1 && af) PBA_LAUNCH_ONE(PPL, 1, AffineF32)           \
-  else if (mode == 0 && af) PBA_LAUNCH_ONE(PPL, 0, AffineF32)      \
-  else if (mode == 2 && af) PBA_LAUNCH_ONE(PPL, 2, AffineF32)      \
-  else if (mode == 1 && in) PBA_LAUNCH_ONE(PPL, 1, IntrF32)        \
-  else if (mode == 0 && in) PBA_LAUNCH_ONE(PPL, 0, IntrF32)        \
-  else if (mode == 1 && hs) PBA_LAUNCH_ONE(PPL, 1, ScaledF16)      \
-  else if (mode == 0 && hs) PBA_LAUNCH_ONE(PPL, 0, ScaledF16)      \
-  else if (mode == 1 && h) PBA_LAUNCH_ONE(PPL, 1, _Float16)        \
-  else if (mode == 1) PBA_LAUNCH_ONE(PPL, 1, float)                \
-  else if (mode == 0 && h) PBA_LAUNCH_ONE(PPL, 0, _Float16)        \
-  else if (mode == 0) PBA_LAUNCH_ONE(PPL, 0, float)                \
-  else PBA_LAUNCH_ONE(PPL, 2, float)
-  const int ppl = (e->P + 7) / 8;
-  if (ppl == 2) { PBA_LAUNCH_PPL(2) }
-  else if (ppl == 3) { PBA_LAUNCH_PPL(3) }
-  else { PBA_LAUNCH_PPL(4) }
-#undef PBA_LAUNCH_PPL
-#undef PBA_LAUNCH_ONE
-}
-
-void launch_mode(pba_engine* e, const KernelArgs& ka, int mode) {
-  if (e->opt.residual_kind == PBA_RESIDUAL_GEOMETRIC) {
-    switch (e->opt.camera_model) {
-      case PBA_CAMERA_PINHOLE: launch_geometric<CAM_PINHOLE>(e, ka, mode); break;
-      case PBA_CAMERA_DOUBLE_SPHERE: launch_geometric<CAM_DS>(e, ka, mode); break;
-      case PBA_CAMERA_EUCM: launch_geometric<CAM_EUCM>(e, ka, mode); break;
-      default: launch_geometric<CAM_KB4>(e, ka, mode); break;
-    }
-    return;
-  }
-  switch (e->opt.camera_model + 4 * e->interp) {
-    case 0: launch_photometric<0>(e, ka, mode); break;
-    case 1: launch_photometric<1>(e, ka, mode); break;
-    case 2: launch_photometric<2>(e, ka, mode); break;
-    case 3: launch_photometric<3>(e, ka, mode); break;
-    case 4: launch_photometric<4>(e, ka, mode); break;
-    case 5: launch_photometric<5>(e, ka, mode); break;
-    case 6: launch_photometric<6>(e, ka, mode); break;
-    default: launch_photometric<7>(e, ka, mode); break;
-  }
-}
-
 }  // namespace
 
 namespace pba {
 namespace detail {
-
-KernelArgs make_kernel_args(pba_engine* e, const PairRec* pairs, const double* rho) {
-  KernelArgs ka{};
-  ka.images = e->images.p;
-  ka.width = e->width;
-  ka.height = e->height;
-  ka.tiles_x = tiles_x_of(e->width);
-  ka.frame_stride = tiled_frame_bytes(e->width, e->height);
-  ka.umax = e->width + 1.0;
-  ka.vmax = e->height + 1.0;
-  ka.intr = e->intr.p;
-  ka.intr_d = e->intr_d.p;
-  ka.intr_t = e->opt_intr ? e->intr_state.p : e->intr.p;
-  ka.intr_t_d = e->opt_intr ? e->intr_state_d.p : e->intr_d.p;
-  ka.intr_scale = std::ldexp(1.0f, -e->level);
-  ka.block_point = e->block_point.p;
-  ka.block_pair = e->block_pair.p;
-  ka.block_pp = e->block_pp.p;
-  ka.pairs = pairs;
-  ka.block_rec = e->block_rec.p;
-  ka.n_pose_d = 7 * e->n_frames;
-  ka.n_points = e->n_points;
-  ka.u_ref = e->u_ref.p;
-  ka.host_int = e->host_int.p;
-  ka.rho = rho;
-  ka.u_obs = e->u_obs.p;
-  if (e->affine) ka.affine = e->affine_state.p;  // (photometric: u_obs unused, the slot is shared)
-  ka.out = e->out.p;
-  ka.cost = e->cost.p;
-  ka.valid = e->valid.p;
-  ka.n_blocks = e->n_blocks;
-  ka.n_cams = e->n_cams;
-  ka.P = e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC ? e->P : 2;
-  ka.huber = e->opt.huber_width;
-  for (size_t i = 0; i < e->pattern_h.size() && i < 2 * PBA_MAX_PATTERN; ++i) ka.pattern[i] = e->pattern_h[i];
-  return ka;
-}
 
 void launch_pairs(pba_engine* e, const double* poses, PairRec* pairs) {
   // a photometric pair's target part is the intrinsics state's (the geometric kernels read the state themselves and
@@ -883,20 +122,6 @@ void launch_pairs(pba_engine* e, const double* poses, PairRec* pairs) {
   pair_kernel<<<(e->n_pairs + 255) / 256, 256, 0, e->stream>>>(poses, e->pair_host.p, e->pair_target.p, e->frame_cam.p,
                                                                e->intr_d.p, state ? e->intr_state_d.p : e->intr_d.p,
                                                                pairs, e->n_pairs);
-}
-
-int launch_cost_only(pba_engine* e, const PairRec* pairs, const double* rho, double* wg_red, int* n_slots,
-                     const double* poses, const float* intr_t, const double* intr_t_d, const double* affine) {
-  KernelArgs ka = make_kernel_args(e, pairs, rho);
-  ka.poses = poses;
-  if (affine && e->affine) ka.affine = affine;
-  if (intr_t) ka.intr_t = intr_t;
-  if (intr_t_d) ka.intr_t_d = intr_t_d;
-  ka.wg_red = wg_red;
-  launch_mode(e, ka, 2);
-  if (n_slots) *n_slots = e->last_grid;
-  PBA_HIP(hipGetLastError());
-  return PBA_OK;
 }
 
 }  // namespace detail
@@ -1567,19 +792,14 @@ int pba_get_records(pba_engine* e, float* records, uint8_t* valid) {
   }
   if (valid) PBA_HIP(hipMemcpyAsync(valid, e->valid.p, e->n_blocks, hipMemcpyDeviceToHost, e->stream));
   PBA_HIP(hipStreamSynchronize(e->stream));
-  if (scaled && records) {  // [r | J_host | J_target | J_rho | e]: a Jacobian entry of pixel row k is stored · e[k]
-    const size_t R = (size_t)e->R();
+  if (scaled && records) {  // a Jacobian entry of pixel row k is stored divided by e[k] (as decode_records_kernel)
+    const int R = e->R();
     for (size_t b = 0; b < (size_t)e->n_blocks; ++b) {
-      const _Float16* s = half.data() + b * 15 * R;
-      float* d = records + b * 14 * R;
-      for (size_t k = 0; k < R; ++k) {
-        const float sc = (float)s[14 * R + k];
-        d[k] = (float)s[k];
-        for (size_t j = 0; j < 6; ++j) {
-          d[R + 6 * k + j] = (float)s[R + 6 * k + j] * sc;
-          d[7 * R + 6 * k + j] = (float)s[7 * R + 6 * k + j] * sc;
-        }
-        d[13 * R + k] = (float)s[13 * R + k] * sc;
+      const _Float16* s = half.data() + b * (RecFormat<ScaledF16>::kCols * R);
+      float* d = records + b * col_tail(R);
+      for (int c = 0; c < col_tail(R); ++c) {
+        const int row = scale_row_of(c, R);
+        d[c] = row < 0 ? (float)s[c] : (float)s[c] * (float)s[col_tail(R) + row];
       }
     }
   } else {
@@ -1786,17 +1006,7 @@ int pba_decode_records_device(pba_engine* e, float* d_out) {
   if (!e || !d_out) return fail(PBA_ERR_INVALID_ARGUMENT, "null argument");
   if (!e->evaluated) return fail(PBA_ERR_NOT_READY, "pba_evaluate first");
   if (int rc = check_device(e)) return rc;
-  if (e->record_format == PBA_RECORD_F32) {
-    PBA_HIP(hipMemcpyAsync(d_out, e->out.p, (size_t)e->n_blocks * e->rec_floats() * sizeof(float),
-                           hipMemcpyDeviceToDevice, e->stream));
-    return PBA_OK;
-  }
-  const int grid = (e->n_blocks + kDecodeBlocks - 1) / kDecodeBlocks;
-  decode_records_kernel<<<grid, kBlockThreads, 0, e->stream>>>(reinterpret_cast<const _Float16*>(e->out.p), d_out,
-                                                               e->n_blocks, e->P,
-                                                               e->record_format == PBA_RECORD_F16_SCALED ? 15 : 14);
-  PBA_HIP(hipGetLastError());
-  return PBA_OK;
+  return launch_decode_records(e, d_out);
 }
 
 }  // extern "C"

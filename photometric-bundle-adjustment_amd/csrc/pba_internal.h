@@ -1,5 +1,5 @@
 // pba_internal.h — engine state, kernel argument blocks and the per-row residual/Jacobian arithmetic
-// shared by the Ceres-mode kernels (pba_engine.hip) and the Gauss-Newton kernels (pba_gn*.hip).
+// shared by the Ceres-mode kernels (pba_evaluate.hip) and the Gauss-Newton kernels (pba_gn*.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -999,10 +999,17 @@ inline int check_device(pba_engine* e) {
   return PBA_OK;
 }
 
-// Kernel arguments describing the engine's current problem and state.
+// Kernel arguments describing the engine's current problem and state (pba_evaluate.hip, as the three launches below).
 KernelArgs make_kernel_args(pba_engine* e, const PairRec* pairs, const double* rho);
 
-// Pair kernel launch (relative poses of every (host, target) pair from an fp64 pose array).
+// One evaluation launch of the engine's residual kind, camera model and record format: mode 1 records (residuals and
+// Jacobians), 0 residuals only, 2 per-block costs and validity only.
+void launch_mode(pba_engine* e, const KernelArgs& ka, int mode);
+
+// The engine's records as 14·R fp32 values per block into d_out (pba_decode_records_device after its checks).
+int launch_decode_records(pba_engine* e, float* d_out);
+
+// Pair kernel launch (relative poses of every (host, target) pair from an fp64 pose array; pba_engine.hip).
 void launch_pairs(pba_engine* e, const double* poses, PairRec* pairs);
 
 // Residual-only evaluation writing only per-block costs/validity (state given by pairs/rho).

@@ -177,6 +177,26 @@ def test_decoded_records_match_fp32_without_clipping(P, path):
 
 
 @pytest.mark.parametrize("P,path", CASES)
+def test_half_records_saturate_at_the_half_range(P, path):
+    """PBA_RECORD_F16 saturates at ±65504 (include/pba.h): with a the fp32 record and h the raw halves of the valid
+    blocks, every half is finite, |a| ≥ 65536 gives exactly ±65504 with a's sign, and |a| ≤ 65000 stays within the range.
+    The band between is left out: the fp32 and the half instantiations may contract their arithmetic differently (the
+    1e-6 allowance above), so an entry next to 65520 may round to either side there.  It holds at most 0.1 % of the
+    Jacobian entries, and at least 1000 entries lie beyond it."""
+    c = run_case(P, path)
+    m = c["f32"]["valid"].astype(bool)
+    assert np.array_equal(c["f16"]["valid"], c["f32"]["valid"])
+    a, h = c["f32"]["rec"][m].astype(np.float64), halves(c["f16"]["raw"][m])
+    assert a.shape == h.shape
+    big, small = np.abs(a) >= 65536.0, np.abs(a) <= 65000.0
+    assert big.sum() >= 1000, int(big.sum())
+    assert (~big & ~small)[:, P:].mean() <= 1e-3, int((~big & ~small).sum())
+    assert np.isfinite(h).all()
+    assert np.array_equal(h[big], np.copysign(65504.0, a[big]))
+    assert (np.abs(h[small]) <= 65504.0).all()
+
+
+@pytest.mark.parametrize("P,path", CASES)
 def test_host_numpy_and_device_decodes_agree_bitwise(P, path):
     c = run_case(P, path)
     s = c["scaled"]
