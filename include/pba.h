@@ -262,6 +262,45 @@ int pba_affine_step(pba_engine* engine, double lambda, double* model_decrease, i
 int pba_affine_get_step(pba_engine* engine, double* d_ab);
 int pba_affine_candidate_cost(pba_engine* engine, double* cost);
 int pba_affine_accept(pba_engine* engine);
+/* The joint solve of poses, inverse distances and brightness (photometric engines with pba_set_affine_brightness; no
+ * opt-in: the entry points are new, and pba_gn_* and pba_affine_* behave as before).  Exactly a Ceres solve with every
+ * parameter block of the 18·P record free: 8 unknowns per keyframe, [δpose (6, right update T·exp δ) | δa δb], and one δρ
+ * per point, with the pose solve's rules — per-block Huber through the Corrector (corrector.cc:42-110, ρ'' ≤ 0:
+ * J̃ = √ρ' J, r̃ = √ρ' r; w = ρ'(Σr²) in the linearisation's own float arithmetic, a block out exactly when the other
+ * solves count it invalid), cost Σ ½ρ(‖r‖²), damping (H + λ·clamp(diag H, 1e-6, 1e32)) δ = −g
+ * (levenberg_marquardt_strategy.cc), the ρ eliminated into the 8·n_frames reduced system S δ_kf = −g_S
+ * (schur_complement_solver.cc), δρ = −(g_ρ + Wᵀδ_kf)/H'_ρρ, model decrease ½(λ δᵀDδ − gᵀδ) over all free unknowns,
+ * candidate T·exp(δpose), ρ + δρ, (a, b) + (δa, δb).
+ * Constants (Problem::SetParameterBlockConstant, problem.h:306) get identity rows, a zero gradient and a zero step, the
+ * two halves of a keyframe independently: its pose when it is in pba_set_fixed_frames or has no valid block; its (a, b)
+ * when it is in pba_set_fixed_affine_frames (the brightness solve's call, reused), has no valid block, or has a
+ * non-finite a or b.  AT LEAST ONE KEYFRAME'S (a, b) MUST BE CONSTANT: adding a common offset to every a, or any
+ * consistent shift of the b's, leaves every residual unchanged, so with none fixed the undamped reduced system is
+ * singular (measured smallest eigenvalue −5e-8, against 0.76 with keyframe 0 fixed); with λ > 0 the system is definite
+ * either way.  pba_joint_step: solver_status ≠ 0 and no candidate when the damped reduced system is not positive
+ * definite, as pba_gn_step.
+ * pba_joint_get_reduced_system: the last step's system, dense (row-major, n = pba_joint_system_size = 8·n_frames), damped,
+ * constants as identity / 0, and g_S — testing and inspection.  pba_joint_get_step: δ of the keyframes (8·n_frames) and
+ * δρ (n_points); either may be NULL.  pba_joint_accept: poses, ρ and affine state ← candidate.
+ * Every sum is fp64 in a fixed order, so results are bitwise reproducible.  They work at the engine's current pyramid
+ * level; (a, b) carry no level factor.  Single GPU.
+ * pba_solve_joint: Ceres' trust-region loop (trust_region_minimizer.cc:67-136) driven from the host as pba_solve_affine
+ * is, norms over the free poses (ambient [q | t]), the ρ of points with blocks and the free (a, b); a candidate with
+ * fewer valid blocks than the current state counts as a failed evaluation (pba_solve's rule); fills the summary (the
+ * device phase times stay 0) and the trajectory pba_solver_iterations serves.
+ * Stale: pba_set_state*, pba_set_affine_state*, pba_set_fixed_frames, pba_set_fixed_affine_frames, pba_set_level,
+ * pba_joint_accept, pba_affine_accept and pba_gn_accept (pba_solve, pba_solve_affine) leave a joint linearisation stale:
+ * step, candidate cost, accept and the getters then return PBA_ERR_NOT_READY until pba_joint_linearize.
+ * PBA_ERR_INVALID_ARGUMENT, nothing changed, on a geometric engine or without pba_set_affine_brightness (so never with
+ * half records or free intrinsics, which affine brightness refuses); PBA_ERR_NOT_READY for a call before the one it
+ * follows (step before linearize; candidate cost, accept and the getters before a step that succeeded). */
+int pba_joint_linearize(pba_engine* engine, double* cost);  /* cost may be NULL */
+int pba_joint_system_size(pba_engine* engine, int32_t* n);  /* 8·n_frames */
+int pba_joint_step(pba_engine* engine, double lambda, double* model_decrease, int32_t* solver_status);
+int pba_joint_get_reduced_system(pba_engine* engine, double* S_dense, double* g);
+int pba_joint_get_step(pba_engine* engine, double* d_keyframes, double* d_inv_dist);
+int pba_joint_candidate_cost(pba_engine* engine, double* cost);
+int pba_joint_accept(pba_engine* engine);
 /* Image interpolator of the photometric residual (and of the device-sampled I_h,k): PBA_INTERP_BILINEAR (default,
  * the north star's) or PBA_INTERP_BICUBIC — Ceres' BiCubicInterpolator over Grid2D<uint8_t, 1>
  * (cubic_interpolation.h:252-344, edge clamp :403-414), the interpolator of PhotometricError<8>
@@ -395,6 +434,8 @@ typedef struct pba_iteration_summary {
 int pba_solver_iterations(const pba_engine* engine, int32_t capacity, pba_iteration_summary* out, int32_t* count);
 /* the brightness solve's LM loop (see pba_affine_linearize above) */
 int pba_solve_affine(pba_engine* engine, const pba_solver_options* options, pba_solver_summary* summary);
+/* the joint solve's LM loop (see pba_joint_linearize above) */
+int pba_solve_joint(pba_engine* engine, const pba_solver_options* options, pba_solver_summary* summary);
 
 /* constant parameter blocks (Problem::SetParameterBlockConstant, map_utils.h:334-336) */
 int pba_set_fixed_frames(pba_engine* engine, int32_t n, const int32_t* frames);

@@ -456,6 +456,7 @@ int accept_ab(pba_engine* e) {
   PBA_HIP(hipMemcpyAsync(e->affine_state.p, e->aff.ab_new.p, sizeof(double) * 2 * (size_t)e->n_frames,
                          hipMemcpyDeviceToDevice, e->stream));
   e->aff.linearized = e->aff.have_step = false;
+  e->joint.linearized = false;
   e->evaluated = false;
   e->res_fresh = false;
   return PBA_OK;
@@ -500,6 +501,7 @@ int pba_set_fixed_affine_frames(pba_engine* e, int32_t n, const int32_t* frames)
   }
   e->aff.fixed_h = f;
   e->aff.linearized = e->aff.have_step = false;
+  e->joint.linearized = false;
   return PBA_OK;
 }
 

@@ -338,12 +338,14 @@ int pba_set_affine_state(pba_engine* e, const double* ab) {
   if (int rc = affine_state_ready(e, ab)) return rc;
   PBA_HIP(hipMemcpyAsync(e->affine_state.p, ab, sizeof(double) * 2 * (size_t)e->n_frames, hipMemcpyHostToDevice, e->stream));
   PBA_HIP(hipStreamSynchronize(e->stream));  // (the caller's memory is free to change on return)
+  e->joint.linearized = false;
   return PBA_OK;
 }
 
 int pba_set_affine_state_device(pba_engine* e, const double* d_ab) {
   if (int rc = affine_state_ready(e, d_ab)) return rc;
   PBA_HIP(hipMemcpyAsync(e->affine_state.p, d_ab, sizeof(double) * 2 * (size_t)e->n_frames, hipMemcpyDeviceToDevice, e->stream));
+  e->joint.linearized = false;
   return PBA_OK;
 }
 
@@ -467,6 +469,7 @@ static int set_frames_impl(pba_engine* e, int32_t n_frames, const int32_t* frame
   e->aff.planned = false;
   e->aff.fixed_h.clear();
   e->aff.linearized = e->aff.have_step = false;
+  e->joint.planned = e->joint.linearized = false;
   e->n_frames = n_frames;
   e->width = width;
   e->height = height;
@@ -526,6 +529,7 @@ int pba_set_points(pba_engine* e, int32_t n_points, const int32_t* host_frame, c
   PBA_HIP(hipStreamSynchronize(e->stream));
   e->point_host_h.assign(host_frame, host_frame + n_points);
   e->state_set = false;
+  e->joint.planned = e->joint.linearized = false;
   return PBA_OK;
 }
 
@@ -598,6 +602,7 @@ int pba_set_blocks(pba_engine* e, int32_t n_blocks, const int32_t* block_point, 
   e->gn.prepared = false;
   e->aff.planned = false;
   e->aff.linearized = e->aff.have_step = false;
+  e->joint.planned = e->joint.linearized = false;
   return upload_block_records(e);
 }
 
@@ -610,6 +615,7 @@ int pba_set_state(pba_engine* e, const double* poses, const double* inv_dist) {
   PBA_HIP(hipMemcpyAsync(e->rho.p, inv_dist, (size_t)e->n_points * sizeof(double), hipMemcpyHostToDevice, e->stream));
   e->state_set = true;
   e->pairs_fresh = false;
+  e->joint.linearized = false;
   return PBA_OK;
 }
 
@@ -630,6 +636,7 @@ int pba_set_state_device(pba_engine* e, const double* d_poses, const double* d_i
   PBA_HIP(hipGetLastError());
   e->state_set = true;
   e->pairs_fresh = table;
+  e->joint.linearized = false;
   return PBA_OK;
 }
 

@@ -1831,6 +1831,7 @@ static int candidate_cost(pba_engine* e, double* cost) {
 
 static int accept(pba_engine* e) {
   launch_accept(e, nullptr);
+  e->joint.linearized = false;
   PBA_HIP(hipGetLastError());
   // a photometric engine's host copy of the (level-0) intrinsics state follows the device state
   if (e->gn.nc_sys) return download_intrinsics_state(e);
@@ -1963,6 +1964,7 @@ int pba_set_fixed_frames(pba_engine* e, int32_t n, const int32_t* frames) {
   }
   e->gn.fixed_h = f;
   e->gn.prepared = false;
+  e->joint.linearized = false;
   return PBA_OK;
 }
 

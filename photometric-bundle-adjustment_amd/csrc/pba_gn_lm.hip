@@ -504,6 +504,7 @@ extern "C" {
 
 int pba_solve(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum) {
   if (int rc = ensure_prepared(e)) return rc;
+  e->joint.linearized = false;  // (the solve moves the state)
   return solve_single(e, o, sum);
 }
 

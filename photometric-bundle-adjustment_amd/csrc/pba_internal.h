@@ -921,8 +921,31 @@ struct AffineSolve {
   bool linearized = false, have_step = false;
 };
 
+// The joint solve of poses, inverse distances and brightness (pba_joint.hip; photometric engines with
+// pba_set_affine_brightness): its plan (pba_joint_plan.h) on the device, the per-block moment records, the pieces of
+// the normal equations, the reduced system as an 8×8-block skyline, its factor and the candidate state.  The layouts
+// are in pba_joint.hip.
+struct JointSolve {
+  bool planned = false;            // cleared when the frames, points or blocks change
+  bool linearized = false;         // cleared by whatever moves the state or the constants (pba.h: "stale")
+  bool have_step = false;
+  int n_sky = 0, lin_slots = 0, upd_slots = 0, pt_slots = 0;
+  double n_valid = 0.0;            // valid blocks of the linearisation
+  std::vector<int> first_h, row_h;
+  pba::detail::DevBuf<int> pair_ptr, pair_blocks, frame_ptr, frame_pairs, pt_ptr, pt_blocks, first, row, colptr, colrows,
+      off_ptr, off_pairs, term_ptr, fe_ptr, fe_entries, sky_i, sky_j;
+  pba::detail::DevBuf<int2> terms;
+  pba::detail::DevBuf<uint8_t> fixed, cst;  // 2 per keyframe (pose, (a, b)): requested / effective constants
+  pba::detail::DevBuf<double> rec, pair_rec, pair_ad, blk_data, pt_data, inv, frame_data, gmax_f, gmax_p;
+  pba::detail::DevBuf<double> S, L, Linv, g, x, drho;
+  pba::detail::DevBuf<double> poses_new, rho_new, ab_new;
+  pba::detail::DevBuf<double> red, red3;
+  pba::detail::DevBuf<int> status;
+};
+
 struct pba_engine {
   AffineSolve aff;
+  JointSolve joint;
   pba_options opt{};
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;

@@ -1,0 +1,1136 @@
+// pba_joint.hip — the joint solve of poses, inverse distances and affine brightness (include/pba.h pba_joint_*,
+// pba_solve_joint): photometric engines with pba_set_affine_brightness.
+//
+// Unknowns: 8 per keyframe, [δpose (6, T·exp δ) | δa δb], and one δρ per point.  A block (host h, target t, point p) has
+// the rows J = [J_h | J_ab,h | J_t | J_ab,t | J_ρ] and r of the 18·P record.  With Ad the adjoint of T_th,
+// [hv hw] = −[tv tw]·Ad (pba_gn_linearize.hip), and with E = exp(a_t − a_h), c_k = I_h,k − b_h,
+// J_ab,h = [E·c, E], J_ab,t = [−E·c, −1]: every column is a combination of the ten columns
+//   x = [tv(3) tw(3) jr c 1 r],
+// so a block's whole contribution to the normal equations is w·xᵀx (w = ρ′(Σr²), Ceres' Corrector with ρ″ ≤ 0) — 55
+// doubles whatever P — and Ad and E are the pair's.
+//
+// Moment record, 64 doubles per block (joint_moments_kernel): [0, 55) the upper triangle of w·xᵀx, row-major
+// (up(i, j) = 10·i − i(i−1)/2 + j − i, i ≤ j); 55 w; 56 E; 57 the block's cost ½ρ(Σr²); 58 valid (1 / 0); 59…63 zero.
+// An invalid block's record is all zeros.
+// Pair record, kPairRec doubles (joint_pair_kernel): the 16×16 JᵀwJ over [pose_h(6) a_h b_h pose_t(6) a_t b_t], row
+// major; 256 the 16 gradient entries; 272 the pair's valid blocks.  pair_ad: Ad (36, row-major) and E.
+// Block data, kBlk doubles (joint_block_kernel): H_ρρ, g_ρ, W_t(8), W_h(8) with W = JᵀwJ_ρ.
+// Point data, kPt doubles (joint_point_kernel): H_ρρ, g_ρ, has blocks, 0, W_h(8) summed over its blocks.
+// Frame data, kFrame doubles (joint_frame_kernel): the direct gradient (8) and the direct diagonal (8).
+// Everything across blocks is fp64 in the fixed order of the host-built lists (pba_joint_plan.h), without atomics.
+// The reduced system is an 8×8-block lower skyline over the pose system's profile, damped as Ceres' LM strategy does
+// (levenberg_marquardt_strategy.cc) and factored right-looking by one workgroup (joint_solve_kernel, modelled on
+// skyline_solve_kernel).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cfloat>
+#include <cmath>
+#include <vector>
+
+#include "pba_internal.h"
+#include "pba_joint_plan.h"
+
+using namespace pba;
+using namespace pba::detail;
+
+namespace {
+
+constexpr int kCols = 10;      // x = [tv tw jr c 1 r]
+constexpr int kMom = 55;       // upper triangle of xᵀx
+constexpr int kRec = 64;       // doubles per block moment record
+constexpr int kPairRec = 280;  // doubles per pair record (256 + 16 + valid, padded)
+constexpr int kPairAd = 40;    // Ad (36), E, padding
+constexpr int kBlk = 20;       // H_ρρ, g_ρ, W_t(8), W_h(8), padding
+constexpr int kPt = 12;        // H_ρρ, g_ρ, has blocks, 0, W_h(8)
+constexpr int kFrame = 16;     // direct gradient (8), direct diagonal (8)
+
+__host__ __device__ constexpr int up(int i, int j) { return 10 * i - i * (i - 1) / 2 + (j - i); }  // i ≤ j < 10
+static_assert(up(9, 9) == kMom - 1, "upper triangle of 10 columns");
+
+__device__ __forceinline__ double lm_clamp(double d) { return fmin(fmax(d, 1e-6), 1e32); }
+
+// Producer.  The layout of affine_moments_kernel: 8 lanes per block, ⌈P/8⌉ rows per lane (a launch scalar), the
+// fused-state prologue (a.poses), block_affine and photometric_row<…, JAC, …, AFF> — the record path's rows.  Each pass
+// stages its 8 rows per block in LDS and the block's lanes deal the 55 moments among them (lane k: moments k, k + 8, …),
+// summing the rows in pixel order: a fixed order, no atomics.  Products of fp32 values are exact in fp64.  ρ′ and the
+// block's validity are formed as the linearisation forms them (fp32 Σr² per lane, the DPP group sum, huber_weight) and
+// ρ′ scales the moments after the last pass.
+template <int PM>
+__global__ __launch_bounds__(kBlockThreads) void joint_moments_kernel(const KernelArgs a, double* __restrict__ rec,
+                                                                     int ppl) {
+  constexpr int LPB = 8, BPW = kBlockThreads / LPB, NQ = (kMom + LPB - 1) / LPB;
+  __shared__ __attribute__((aligned(16))) TileBlock s_tb[BPW];
+  __shared__ float2 s_pat[PBA_MAX_PATTERN];
+  __shared__ float s_x[BPW][LPB][kCols];
+  const int P = a.P;
+  const int blk0 = logical_tile() * BPW;
+  const int lb = threadIdx.x / LPB, k = threadIdx.x % LPB;
+  const int blk = blk0 + lb;
+  const bool live = blk < a.n_blocks;
+  const int bq = live ? blk : a.n_blocks - 1;  // a dead block evaluates the last block, masked below
+  for (int i = threadIdx.x; i < P; i += kBlockThreads) s_pat[i] = make_float2(a.pattern[2 * i], a.pattern[2 * i + 1]);
+  const int pt = stage_tile<LPB>(a, s_tb, lb, k, blk, live);
+  const Affine af = block_affine(a, bq);
+  int mi[NQ], mj[NQ];  // this lane's moments (i ≤ j); a lane past the last moment repeats moment 0 and does not store
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int m = k + LPB * q;
+    int i = 0, rem = m < kMom ? m : 0;
+    while (rem >= kCols - i) {
+      rem -= kCols - i;
+      ++i;
+    }
+    mi[q] = i;
+    mj[q] = i + rem;
+  }
+  __syncthreads();
+  int okl = 1;
+  float s = 0.0f;
+  double acc[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+  for (int j = 0; j < ppl; ++j) {
+    const int px = k + LPB * j;
+    const bool act = live && px < P;
+    const float Ih = act ? a.host_int[(long long)pt * P + px] : 0.0f;
+    const Row row = photometric_row<PM, true, TileBlock, false, false, true>(a, s_tb[lb], s_pat[act ? px : 0], Ih,
+                                                                              nullptr, nullptr, &af);
+    const bool use = act && row.ok;
+    okl &= act ? row.ok : 1;
+    s += use ? row.r * row.r : 0.0f;
+    float* x = s_x[lb][k];
+    x[0] = use ? row.tv.x : 0.0f;
+    x[1] = use ? row.tv.y : 0.0f;
+    x[2] = use ? row.tv.z : 0.0f;
+    x[3] = use ? row.tw.x : 0.0f;
+    x[4] = use ? row.tw.y : 0.0f;
+    x[5] = use ? row.tw.z : 0.0f;
+    x[6] = use ? row.jr : 0.0f;
+    x[7] = use ? Ih - af.bh : 0.0f;
+    x[8] = use ? 1.0f : 0.0f;
+    x[9] = use ? row.r : 0.0f;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+      for (int r = 0; r < LPB; ++r) acc[q] += (double)s_x[lb][r][mi[q]] * (double)s_x[lb][r][mj[q]];
+    __syncthreads();
+  }
+  const int ok = group_all<LPB>(okl);
+  s = group_sum<LPB>(s);
+  const float w = ok ? huber_weight(s, a.huber) : 0.0f;
+  const float bc = ok ? huber_cost(s, a.huber) : 0.0f;
+  if (live) {
+    double* o = rec + (long long)blk * kRec;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int m = k + LPB * q;
+      if (m < kMom) o[m] = ok ? (double)w * acc[q] : 0.0;
+    }
+    // the tail: 55 w, 56 E, 57 cost, 58 valid, 59…63 zero — one value per lane, lane 7 the last two
+    const double tail = k == 0 ? (double)w : k == 1 ? (ok ? (double)af.E : 0.0) : k == 2 ? (double)bc : k == 3 ? (ok ? 1.0 : 0.0) : 0.0;
+    o[kMom + k] = tail;
+    if (k == LPB - 1) o[kRec - 1] = 0.0;
+  }
+  if (a.wg_red) {
+    const bool one = live && k == 0;
+    wg_reduce2(one ? (double)bc : 0.0, one && ok ? 1.0 : 0.0, a.wg_red + 2 * logical_tile());
+  }
+}
+
+struct RelPose {  // pair_rotation / pair_translation's fields
+  double R[9], t[3];
+  float Rf[9], tf[3];
+};
+
+// One 64-thread workgroup per pair: its blocks' moments summed in block order, then JᵀwJ = Mᵀ(Σ w xᵀx)M and
+// Jᵀwr = Mᵀ(Σ w xᵀr) with the 10×16 map M from x to [J_h | J_ab,h | J_t | J_ab,t]: J_h = −J_t·Ad, J_ab,h = [E·c, E],
+// J_ab,t = [−E·c, −1].  Ad = [[R, [t]×R], [0, R]] of T_th from the two state poses in fp64 (form_pair's arithmetic).
+__global__ __launch_bounds__(64) void joint_pair_kernel(const double* __restrict__ rec, const int* __restrict__ pair_ptr,
+                                                        const int* __restrict__ pair_blocks,
+                                                        const int* __restrict__ pair_host,
+                                                        const int* __restrict__ pair_target,
+                                                        const double* __restrict__ poses, double* __restrict__ pair_rec,
+                                                        double* __restrict__ pair_ad) {
+  __shared__ double sQ[kCols][kCols], sM[kCols][16], sT[kCols][16], sAd[36], sE[2];
+  const int p = blockIdx.x, t = threadIdx.x;
+  const int q0 = pair_ptr[p], q1 = pair_ptr[p + 1];
+  if (t < kMom) {
+    double m = 0.0;
+    for (int q = q0; q < q1; ++q) m += rec[(long long)pair_blocks[q] * kRec + t];
+    int i = 0, rem = t;
+    while (rem >= kCols - i) {
+      rem -= kCols - i;
+      ++i;
+    }
+    sQ[i][i + rem] = m;
+    sQ[i + rem][i] = m;
+  } else if (t == kMom) {
+    double E = 0.0, nv = 0.0;  // every valid block of the pair has the pair's E
+    for (int q = q1 - 1; q >= q0; --q) {
+      const double* b = rec + (long long)pair_blocks[q] * kRec;
+      if (b[58] != 0.0) E = b[56];
+      nv += b[58];
+    }
+    sE[0] = E;
+    sE[1] = nv;
+  } else if (t == kMom + 1) {
+    RelPose rp;
+    pair_rotation(poses + 7 * pair_host[p], poses + 7 * pair_target[p], rp);
+    pair_translation(poses + 7 * pair_host[p], poses + 7 * pair_target[p], rp);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        const int r1 = (r + 1) % 3, r2 = (r + 2) % 3;
+        sAd[r * 6 + c] = rp.R[r * 3 + c];
+        sAd[r * 6 + 3 + c] = rp.t[r1] * rp.R[r2 * 3 + c] - rp.t[r2] * rp.R[r1 * 3 + c];
+        sAd[(3 + r) * 6 + c] = 0.0;
+        sAd[(3 + r) * 6 + 3 + c] = rp.R[r * 3 + c];
+      }
+  }
+  __syncthreads();
+  const double E = sE[0];
+  for (int idx = t; idx < kCols * 16; idx += 64) {
+    const int q = idx / 16, c = idx % 16;
+    double v = 0.0;
+    if (c < 6) v = q < 6 ? -sAd[q * 6 + c] : 0.0;
+    else if (c == 6) v = q == 7 ? E : 0.0;
+    else if (c == 7) v = q == 8 ? E : 0.0;
+    else if (c < 14) v = q == c - 8 ? 1.0 : 0.0;
+    else if (c == 14) v = q == 7 ? -E : 0.0;
+    else v = q == 8 ? -1.0 : 0.0;
+    sM[q][c] = v;
+  }
+  __syncthreads();
+  for (int idx = t; idx < kCols * 16; idx += 64) {
+    const int q = idx / 16, c = idx % 16;
+    double v = 0.0;
+    for (int m = 0; m < kCols - 1; ++m) v += sQ[q][m] * sM[m][c];  // (M's row of r is zero)
+    sT[q][c] = v;
+  }
+  __syncthreads();
+  double* o = pair_rec + (long long)p * kPairRec;
+  for (int idx = t; idx < 256; idx += 64) {
+    const int r = idx / 16, c = idx % 16;
+    double v = 0.0;
+    for (int q = 0; q < kCols - 1; ++q) v += sM[q][r] * sT[q][c];
+    o[idx] = v;
+  }
+  if (t < 16) o[256 + t] = sT[kCols - 1][t];
+  if (t == 16) o[272] = sE[1];
+  if (t > 16 && t < 24) o[256 + t] = 0.0;
+  double* ad = pair_ad + (long long)p * kPairAd;
+  if (t < 36) ad[t] = sAd[t];
+  if (t >= 36 && t < kPairAd) ad[t] = t == 36 ? E : 0.0;
+}
+
+// One thread per block: H_ρρ, g_ρ and the two 8-vectors W_t, W_h = JᵀwJ_ρ from its moments of column jr.
+__global__ void joint_block_kernel(const double* __restrict__ rec, const int* __restrict__ block_pair,
+                                   const double* __restrict__ pair_ad, int n_blocks, double* __restrict__ blk_data) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n_blocks) return;
+  const double* m = rec + (long long)b * kRec;
+  const double* ad = pair_ad + (long long)block_pair[b] * kPairAd;
+  const double E = ad[36];
+  double* o = blk_data + (long long)b * kBlk;
+  double t6[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) t6[q] = m[up(q, 6)];
+  const double mc = m[up(6, 7)], m1 = m[up(6, 8)];
+  o[0] = m[up(6, 6)];
+  o[1] = m[up(6, 9)];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) o[2 + q] = t6[q];
+  o[8] = -E * mc;
+  o[9] = -m1;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    double v = 0.0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) v += ad[q * 6 + c] * t6[q];
+    o[10 + c] = -v;
+  }
+  o[16] = E * mc;
+  o[17] = E * m1;
+  o[18] = o[19] = 0.0;
+}
+
+// Σ over the workgroup of N per-lane values and the max of one more, in a fixed order (xor butterflies in each wave,
+// then the waves in order): out[0 … N) the sums, out[N] the max.  Every thread must call it.
+template <int N>
+__device__ __forceinline__ void wg_reduce_n(double (&v)[N], double m, double* out) {
+  __shared__ double s[N + 1][16];
+  for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) v[q] += __shfl_xor(v[q], o, 64);
+    m = fmax(m, __shfl_xor(m, o, 64));
+  }
+  const int w = threadIdx.x / 64, l = threadIdx.x % 64;
+  if (l == 0) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) s[q][w] = v[q];
+    s[N][w] = m;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int nw = (int)(blockDim.x / 64);
+    for (int q = 0; q < N; ++q) {
+      double x = 0.0;
+      for (int i = 0; i < nw; ++i) x += s[q][i];
+      out[q] = x;
+    }
+    double x = 0.0;
+    for (int i = 0; i < nw; ++i) x = fmax(x, s[N][i]);
+    out[N] = x;
+  }
+}
+
+// One thread per point: its blocks' H_ρρ, g_ρ and W_h in block order; per workgroup max |g_ρ| over the points with
+// blocks (the LM loop's gradient norm).
+__global__ __launch_bounds__(256) void joint_point_kernel(const double* __restrict__ blk_data,
+                                                          const int* __restrict__ pt_ptr,
+                                                          const int* __restrict__ pt_blocks, int n_points,
+                                                          double* __restrict__ pt_data, double* __restrict__ gmax_p) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  double gm = 0.0;
+  if (p < n_points) {
+    double H = 0.0, g = 0.0, W[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) W[r] = 0.0;
+    const int q0 = pt_ptr[p], q1 = pt_ptr[p + 1];
+    for (int q = q0; q < q1; ++q) {
+      const double* b = blk_data + (long long)pt_blocks[q] * kBlk;
+      H += b[0];
+      g += b[1];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) W[r] += b[10 + r];
+    }
+    double* o = pt_data + (long long)p * kPt;
+    o[0] = H;
+    o[1] = g;
+    o[2] = q1 > q0 ? 1.0 : 0.0;
+    o[3] = 0.0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) o[4 + r] = W[r];
+    if (q1 > q0) gm = fabs(g);
+  }
+  double none[1] = {0.0};
+  wg_reduce_n<1>(none, gm, gmax_p + 2 * blockIdx.x);
+}
+
+// T·exp(δ) (se3.hpp:763-784), the update of pba_gn.hip's se3_exp_mul
+__device__ void se3_plus(const double* T, const double* d, double* out) {
+  const double w0 = d[3], w1 = d[4], w2 = d[5];
+  const double th2 = w0 * w0 + w1 * w1 + w2 * w2, th = sqrt(th2);
+  double imag, real, A, B;
+  if (th < 1e-10) {
+    real = 1.0 - th2 / 8.0 + th2 * th2 / 384.0;
+    imag = 0.5 - th2 / 48.0 + th2 * th2 / 3840.0;
+    A = 0.5;
+    B = 1.0 / 6.0;
+  } else {
+    double sh, ch;
+    sincos(0.5 * th, &sh, &ch);
+    const double it = rcp_nr(th);
+    real = ch;
+    imag = sh * it;
+    A = 2.0 * imag * imag;
+    B = (th - 2.0 * sh * ch) * (it * it * it);
+  }
+  const double qx = imag * w0, qy = imag * w1, qz = imag * w2, qw = real;
+  const double v0 = d[0], v1 = d[1], v2 = d[2];
+  const double c0 = w1 * v2 - w2 * v1, c1 = w2 * v0 - w0 * v2, c2 = w0 * v1 - w1 * v0;
+  const double cc0 = w1 * c2 - w2 * c1, cc1 = w2 * c0 - w0 * c2, cc2 = w0 * c1 - w1 * c0;
+  const double tx = v0 + A * c0 + B * cc0, ty = v1 + A * c1 + B * cc1, tz = v2 + A * c2 + B * cc2;
+  const double ax = T[0], ay = T[1], az = T[2], aw = T[3];
+  const double rw = aw * qw - ax * qx - ay * qy - az * qz;
+  const double rx = aw * qx + ax * qw + ay * qz - az * qy;
+  const double ry = aw * qy + ay * qw + az * qx - ax * qz;
+  const double rz = aw * qz + az * qw + ax * qy - ay * qx;
+  const double n = rsqrt_nr(rw * rw + rx * rx + ry * ry + rz * rz);
+  double u0 = ay * tz - az * ty, u1 = az * tx - ax * tz, u2 = ax * ty - ay * tx;
+  u0 += u0; u1 += u1; u2 += u2;
+  out[0] = rx * n; out[1] = ry * n; out[2] = rz * n; out[3] = rw * n;
+  out[4] = T[4] + tx + aw * u0 + (ay * u2 - az * u1);
+  out[5] = T[5] + ty + aw * u1 + (az * u0 - ax * u2);
+  out[6] = T[6] + tz + aw * u2 + (ax * u1 - ay * u0);
+}
+
+// One thread per keyframe: the direct gradient and diagonal over its pairs (as host, then as target), its constants —
+// the pose when requested or without a valid block, (a, b) when requested, without a valid block or not finite — and
+// its part of the gradient norm max |x − (x ⊞ −g)| (trust_region_minimizer.cc:312-355) over its free halves.
+__global__ void joint_frame_kernel(const double* __restrict__ pair_rec, const int* __restrict__ frame_ptr,
+                                   const int* __restrict__ frame_pairs, const uint8_t* __restrict__ fixed,
+                                   const double* __restrict__ poses, const double* __restrict__ ab, int n_frames,
+                                   double* __restrict__ frame_data, uint8_t* __restrict__ cst,
+                                   double* __restrict__ gmax_f) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_frames) return;
+  double g[8], d[8], nv = 0.0;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) g[r] = d[r] = 0.0;
+  for (int q = frame_ptr[i]; q < frame_ptr[i + 1]; ++q) {
+    const int e = frame_pairs[q];
+    const double* pr = pair_rec + (long long)(e >> 1) * kPairRec;
+    const int o = (e & 1) ? 8 : 0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      g[r] += pr[256 + o + r];
+      d[r] += pr[(o + r) * 16 + o + r];
+    }
+    nv += pr[272];
+  }
+  const bool seen = nv > 0.0;
+  const bool cp = fixed[2 * i] != 0 || !seen;
+  const bool ca = fixed[2 * i + 1] != 0 || !seen || !isfinite(ab[2 * i]) || !isfinite(ab[2 * i + 1]);
+  cst[2 * i] = cp ? 1 : 0;
+  cst[2 * i + 1] = ca ? 1 : 0;
+  double* o = frame_data + (long long)i * kFrame;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    o[r] = g[r];
+    o[8 + r] = d[r];
+  }
+  double gm = 0.0;
+  if (!cp) {
+    double ng[6], tg[7];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) ng[r] = -g[r];
+    se3_plus(poses + 7 * i, ng, tg);
+#pragma unroll
+    for (int r = 0; r < 7; ++r) gm = fmax(gm, fabs(poses[7 * i + r] - tg[r]));
+  }
+  if (!ca) gm = fmax(gm, fmax(fabs(g[6]), fabs(g[7])));
+  gmax_f[i] = gm;
+}
+
+// Per point: 1 / H′_ρρ, H′ = H + λ·clamp(H, 1e-6, 1e32); 0 for a point without a valid block (no step).
+__global__ void joint_damp_kernel(const double* __restrict__ pt_data, int n_points, double lambda,
+                                  double* __restrict__ inv) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_points) return;
+  const double H = pt_data[(long long)p * kPt];
+  inv[p] = H > 0.0 ? 1.0 / (H + lambda * lm_clamp(H)) : 0.0;
+}
+
+struct AsmArgsJ {
+  const double *pair_rec, *blk_data, *pt_data, *inv, *frame_data;
+  const int *frame_ptr, *frame_pairs, *off_ptr, *off_pairs, *term_ptr, *fe_ptr, *fe_entries, *sky_i, *sky_j, *block_point;
+  const int2* terms;
+  const uint8_t* cst;
+  double *S, *L, *g;
+  int n_frames, n_sky;
+  double lambda;
+};
+
+// W of an entry (pba_joint_plan.h): block e's W_t, or point ~e's W_h; *p its point
+__device__ __forceinline__ const double* entry_w(const AsmArgsJ& a, int e, int* p) {
+  if (e < 0) {
+    *p = ~e;
+    return a.pt_data + (long long)(~e) * kPt + 4;
+  }
+  *p = a.block_point[e];
+  return a.blk_data + (long long)e * kBlk + 2;
+}
+
+// One 64-thread workgroup per lower skyline block (i, j), thread = element (r, c): its pairs' direct terms in list
+// order, then its Schur terms −W_a W_bᵀ/H′_ρρ in list order; then λ·clamp(diag) on the free diagonal and identity rows
+// and columns for the constants.  S keeps the system (pba_joint_get_reduced_system), L is factored in place.
+__global__ __launch_bounds__(64) void joint_assemble_kernel(const AsmArgsJ a) {
+  const int s = blockIdx.x, t = threadIdx.x, r = t >> 3, c = t & 7;
+  const int i = a.sky_i[s], j = a.sky_j[s];
+  double v = 0.0;
+  if (i == j) {
+    for (int q = a.frame_ptr[i]; q < a.frame_ptr[i + 1]; ++q) {
+      const int e = a.frame_pairs[q], o = (e & 1) ? 8 : 0;
+      v += a.pair_rec[(long long)(e >> 1) * kPairRec + (o + r) * 16 + o + c];
+    }
+  } else {
+    for (int q = a.off_ptr[s]; q < a.off_ptr[s + 1]; ++q) {
+      const int e = a.off_pairs[q];
+      const double* pr = a.pair_rec + (long long)(e >> 1) * kPairRec;
+      v += (e & 1) ? pr[(8 + r) * 16 + c] : pr[r * 16 + 8 + c];  // host = column: H_th; host = row: H_ht
+    }
+  }
+  for (int q = a.term_ptr[s]; q < a.term_ptr[s + 1]; ++q) {
+    const int2 tm = a.terms[q];
+    int p, p2;
+    const double* wa = entry_w(a, tm.x, &p);
+    const double* wb = entry_w(a, tm.y, &p2);
+    v -= wa[r] * wb[c] * a.inv[p];
+  }
+  const bool ci = a.cst[2 * i + (r >= 6)] != 0, cj = a.cst[2 * j + (c >= 6)] != 0;
+  if (ci || cj) v = i == j && r == c ? 1.0 : 0.0;
+  else if (i == j && r == c) v += a.lambda * lm_clamp(a.frame_data[(long long)i * kFrame + 8 + r]);
+  a.S[(long long)s * 64 + t] = v;
+  a.L[(long long)s * 64 + t] = v;
+}
+
+// One thread per keyframe unknown: g_S = g − Σ W·g_ρ/H′_ρρ over the entries on the keyframe, 0 for a constant.
+__global__ void joint_gradient_kernel(const AsmArgsJ a) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= 8 * a.n_frames) return;
+  const int i = u >> 3, r = u & 7;
+  double v = a.frame_data[(long long)i * kFrame + r];
+  for (int q = a.fe_ptr[i]; q < a.fe_ptr[i + 1]; ++q) {
+    int p;
+    const double* w = entry_w(a, a.fe_entries[q], &p);
+    v -= w[r] * a.pt_data[(long long)p * kPt + 1] * a.inv[p];
+  }
+  a.g[u] = a.cst[2 * i + (r >= 6)] ? 0.0 : v;
+}
+
+// ---- the reduced solve: S δ = −g, S = LLᵀ in place (8×8-block skyline, right-looking), one workgroup ----------------
+__device__ __forceinline__ bool chol8_reg(const double (&A)[64], double (&L)[64]) {
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 64; ++i) L[i] = 0.0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    double s = A[j * 8 + j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) s -= L[j * 8 + k] * L[j * 8 + k];
+    ok = ok && s > 0.0 && isfinite(s);
+    const double ljj = sqrt(fmax(s, 1e-300));
+    L[j * 8 + j] = ljj;
+#pragma unroll
+    for (int i = j + 1; i < 8; ++i) {
+      double t = A[i * 8 + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) t -= L[i * 8 + k] * L[j * 8 + k];
+      L[i * 8 + j] = t / ljj;
+    }
+  }
+  return ok;
+}
+__device__ __forceinline__ void inv_lower8_reg(const double (&L)[64], double (&Li)[64]) {
+#pragma unroll
+  for (int i = 0; i < 64; ++i) Li[i] = 0.0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    Li[c * 8 + c] = 1.0 / L[c * 8 + c];
+#pragma unroll
+    for (int r = c + 1; r < 8; ++r) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = c; k < r; ++k) s += L[r * 8 + k] * Li[k * 8 + c];
+      Li[r * 8 + c] = -s / L[r * 8 + r];
+    }
+  }
+}
+
+struct SolveArgsJ {
+  double* S;  // the damped system, factored in place
+  const int *first, *row;
+  const double* g;
+  double *Linv, *x;
+  int* status;
+  int N;
+  const int *cptr, *crows;  // column k's profile rows crows[cptr[k] … cptr[k+1]) (every i > k with first(i) ≤ k, in order)
+};
+
+__device__ __forceinline__ long long sky8(const SolveArgsJ& a, int i, int j) {  // block (i, j), j ≥ first(i)
+  return ((long long)a.row[i] + (j - a.first[i])) * 64;
+}
+
+// skyline_solve_kernel with 8×8 blocks: per column k the diagonal block's factor and inverse (one thread, registers), the
+// column panel L_ik = A_ik·L_kk⁻ᵀ four blocks per pass, then the trailing update A_ij −= L_ik L_jkᵀ over the pairs of the
+// column's rows — every element by one thread, the columns in order: a fixed order.  status = k + 1 when column k's
+// pivot is not positive (or not finite).
+__global__ __launch_bounds__(256) void joint_solve_kernel(const SolveArgsJ a) {
+  __shared__ double sA[64], sL[64], sLi[64];
+  __shared__ int s_fail;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_fail = 0;
+  for (int k = 0; k < a.N; ++k) {
+    const long long okk = sky8(a, k, k);
+    if (tid < 64) sA[tid] = a.S[okk + tid];
+    __syncthreads();
+    if (tid == 0) {
+      double A[64], L[64], Li[64];
+#pragma unroll
+      for (int q = 0; q < 64; ++q) A[q] = sA[q];
+      if (!chol8_reg(A, L)) {
+        s_fail = k + 1;
+      } else {
+        inv_lower8_reg(L, Li);
+#pragma unroll
+        for (int q = 0; q < 64; ++q) {
+          sL[q] = L[q];
+          sLi[q] = Li[q];
+        }
+      }
+    }
+    __syncthreads();
+    if (s_fail) {
+      if (tid == 0) *a.status = s_fail;
+      return;
+    }
+    if (tid < 64) {
+      a.S[okk + tid] = sL[tid];
+      a.Linv[(long long)k * 64 + tid] = sLi[tid];
+    }
+    const int c0 = a.cptr[k], na = a.cptr[k + 1] - c0;
+    const int* rows = a.crows + c0;
+    for (int i0 = 0; i0 < na; i0 += 4) {  // (read all, barrier, write)
+      double val = 0.0;
+      long long dst = -1;
+      const int li = i0 + tid / 64;
+      if (li < na) {
+        const int i = rows[li], e = tid % 64, r = e / 8, c = e % 8;
+        const long long o = sky8(a, i, k);
+        for (int m = 0; m <= c; ++m) val += a.S[o + r * 8 + m] * sLi[c * 8 + m];
+        dst = o + e;
+      }
+      __syncthreads();
+      if (dst >= 0) a.S[dst] = val;
+      __threadfence_block();
+      __syncthreads();
+    }
+    const int npairs = na * (na + 1) / 2;
+    for (int idx = tid; idx < npairs * 64; idx += 256) {
+      const int pidx = idx / 64, e = idx % 64, r = e / 8, c = e % 8;
+      int ii = 0;  // lower-triangular pair index → (ii ≥ jj)
+      while ((ii + 1) * (ii + 2) / 2 <= pidx) ++ii;
+      const int jj = pidx - ii * (ii + 1) / 2;
+      const int i = rows[ii], j = rows[jj];
+      const long long oi = sky8(a, i, k), oj = sky8(a, j, k);
+      double s = 0.0;
+      for (int m = 0; m < 8; ++m) s += a.S[oi + r * 8 + m] * a.S[oj + c * 8 + m];
+      a.S[sky8(a, i, j) + e] -= s;
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+  // forward substitution L y = −g (y in x)
+  for (int t = tid; t < 8 * a.N; t += 256) a.x[t] = -a.g[t];
+  __threadfence_block();
+  __syncthreads();
+  for (int k = 0; k < a.N; ++k) {
+    __shared__ double yk[8];
+    if (tid < 8) {
+      double s = 0.0;
+      for (int m = 0; m <= tid; ++m) s += a.Linv[(long long)k * 64 + tid * 8 + m] * a.x[8 * k + m];
+      yk[tid] = s;
+    }
+    __syncthreads();
+    if (tid < 8) a.x[8 * k + tid] = yk[tid];
+    const int c0 = a.cptr[k], na = a.cptr[k + 1] - c0;
+    for (int idx = tid; idx < na * 8; idx += 256) {
+      const int i = a.crows[c0 + idx / 8], r = idx % 8;
+      const long long o = sky8(a, i, k);
+      double s = 0.0;
+      for (int m = 0; m < 8; ++m) s += a.S[o + r * 8 + m] * yk[m];
+      a.x[8 * i + r] -= s;
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+  // back substitution Lᵀ x = y
+  for (int k = a.N - 1; k >= 0; --k) {
+    __shared__ double tk[8];
+    if (tid < 8) {
+      double s = a.x[8 * k + tid];
+      for (int q = a.cptr[k]; q < a.cptr[k + 1]; ++q) {
+        const int i = a.crows[q];
+        const long long o = sky8(a, i, k);
+        for (int m = 0; m < 8; ++m) s -= a.S[o + m * 8 + tid] * a.x[8 * i + m];
+      }
+      tk[tid] = s;
+    }
+    __syncthreads();
+    if (tid < 8) {
+      double s = 0.0;
+      for (int m = tid; m < 8; ++m) s += a.Linv[(long long)k * 64 + m * 8 + tid] * tk[m];
+      a.x[8 * k + tid] = s;
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+  if (tid == 0) *a.status = 0;
+}
+
+struct UpdArgs {
+  const double *x, *pt_data, *blk_data, *inv, *frame_data, *poses, *rho, *ab;
+  const int *pt_ptr, *pt_blocks, *point_host, *status;
+  const int4* block_rec;
+  const uint8_t* cst;
+  double *drho, *poses_new, *rho_new, *ab_new, *red3;
+  int n_points, n_frames;
+  double lambda;
+};
+
+// Threads [0, n_points): δρ = −(g_ρ + Wᵀδ_kf)/H′_ρρ and ρ + δρ.  Threads [n_points, n_points + n_frames): T·exp(δpose),
+// (a, b) + (δa, δb), constants copied.  Per workgroup the parts of 2·model decrease = λ δᵀDδ − gᵀδ, ‖step‖² and
+// ‖candidate‖² in the ambient space of the free unknowns (free poses as [q | t], ρ of points with blocks, free (a, b)).
+// (A constant's step is exactly zero out of the solve: identity rows, zero right-hand side.)
+__global__ __launch_bounds__(256) void joint_update_kernel(const UpdArgs a) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  double v[3] = {0.0, 0.0, 0.0};
+  if (*a.status == 0) {
+    if (u < a.n_points) {
+      const double* pd = a.pt_data + (long long)u * kPt;
+      const double inv = a.inv[u];
+      const int q0 = a.pt_ptr[u], q1 = a.pt_ptr[u + 1];
+      double d = 0.0;
+      if (inv > 0.0) {
+        double acc = pd[1];
+        const double* xh = a.x + 8 * a.point_host[u];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) acc += pd[4 + r] * xh[r];
+        for (int q = q0; q < q1; ++q) {
+          const int b = a.pt_blocks[q];
+          const double* w = a.blk_data + (long long)b * kBlk + 2;
+          const double* xt = a.x + 8 * a.block_rec[b].z;
+#pragma unroll
+          for (int r = 0; r < 8; ++r) acc += w[r] * xt[r];
+        }
+        d = -acc * inv;
+        v[0] = a.lambda * lm_clamp(pd[0]) * d * d - pd[1] * d;
+      }
+      const double rn = a.rho[u] + d;
+      a.drho[u] = d;
+      a.rho_new[u] = rn;
+      if (q1 > q0) {
+        v[1] = d * d;
+        v[2] = rn * rn;
+      }
+    } else if (u < a.n_points + a.n_frames) {
+      const int i = u - a.n_points;
+      const double* fd = a.frame_data + (long long)i * kFrame;
+      const bool cp = a.cst[2 * i] != 0, ca = a.cst[2 * i + 1] != 0;
+      double d[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        d[r] = (r < 6 ? cp : ca) ? 0.0 : a.x[8 * i + r];
+        if (!(r < 6 ? cp : ca)) v[0] += a.lambda * lm_clamp(fd[8 + r]) * d[r] * d[r] - fd[r] * d[r];
+      }
+      double T[7], Tn[7];
+#pragma unroll
+      for (int r = 0; r < 7; ++r) T[r] = Tn[r] = a.poses[7 * i + r];
+      if (!cp) {
+        se3_plus(T, d, Tn);
+#pragma unroll
+        for (int r = 0; r < 7; ++r) {
+          v[1] += (Tn[r] - T[r]) * (Tn[r] - T[r]);
+          v[2] += Tn[r] * Tn[r];
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 7; ++r) a.poses_new[7 * i + r] = Tn[r];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const double o = a.ab[2 * i + r], n = ca ? o : o + d[6 + r];
+        a.ab_new[2 * i + r] = n;
+        if (!ca) {
+          v[1] += d[6 + r] * d[6 + r];
+          v[2] += n * n;
+        }
+      }
+    }
+  }
+  wg_reduce_n<3>(v, 0.0, a.red3 + 4 * blockIdx.x);
+}
+
+template <int PM>
+void launch_moments_pm(pba_engine* e, const KernelArgs& ka, double* rec, int grid) {
+  joint_moments_kernel<PM><<<grid, kBlockThreads, 0, e->stream>>>(ka, rec, (e->P + 7) / 8);
+}
+
+int ready(pba_engine* e) {
+  if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
+  if (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC || !e->affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "the joint solve needs a photometric engine with pba_set_affine_brightness");
+  if (e->opt_intr)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "the joint solve does not combine with pba_set_optimize_intrinsics");
+  if (e->n_blocks <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_blocks first");
+  if (!e->state_set) return fail(PBA_ERR_NOT_READY, "pba_set_state first");
+  if (!e->have_images || e->P <= 0) return fail(PBA_ERR_NOT_READY, "images/pattern missing");
+  if (int rc = check_device(e)) return rc;
+  JointSolve& J = e->joint;
+  if (!J.planned) {
+    JointPlanInput in;
+    in.n_frames = e->n_frames;
+    in.n_pairs = e->n_pairs;
+    in.n_points = e->n_points;
+    in.n_blocks = e->n_blocks;
+    in.pair_host = e->pair_host_h.data();
+    in.pair_target = e->pair_target_h.data();
+    in.block_pair = e->pair_of_h.data();
+    in.block_point = e->block_point_h.data();
+    in.point_host = e->point_host_h.data();
+    JointPlan P;
+    if (!build_joint_plan(in, P)) return fail(PBA_ERR_INVALID_ARGUMENT, "inconsistent pairs (or a block whose target is its host)");
+    const int nf = e->n_frames;
+    std::vector<int> si(P.n_sky), sj(P.n_sky);
+    for (int i = 0; i < nf; ++i)
+      for (int j = P.first[i]; j <= i; ++j) {
+        si[P.row[i] + (j - P.first[i])] = i;
+        sj[P.row[i] + (j - P.first[i])] = j;
+      }
+    std::vector<int2> terms(P.terms.size());
+    for (size_t q = 0; q < terms.size(); ++q) terms[q] = make_int2(P.terms[q].a, P.terms[q].b);
+    PBA_HIP(J.pair_ptr.upload(P.pair_ptr, e->stream));
+    PBA_HIP(J.pair_blocks.upload(P.pair_blocks, e->stream));
+    PBA_HIP(J.frame_ptr.upload(P.frame_ptr, e->stream));
+    PBA_HIP(J.frame_pairs.upload(P.frame_pairs, e->stream));
+    PBA_HIP(J.pt_ptr.upload(P.pt_ptr, e->stream));
+    PBA_HIP(J.pt_blocks.upload(P.pt_blocks, e->stream));
+    PBA_HIP(J.first.upload(P.first, e->stream));
+    PBA_HIP(J.row.upload(P.row, e->stream));
+    PBA_HIP(J.colptr.upload(P.colptr, e->stream));
+    PBA_HIP(J.colrows.upload(P.colrows, e->stream));
+    PBA_HIP(J.off_ptr.upload(P.off_ptr, e->stream));
+    PBA_HIP(J.off_pairs.upload(P.off_pairs, e->stream));
+    PBA_HIP(J.term_ptr.upload(P.term_ptr, e->stream));
+    PBA_HIP(J.terms.upload(terms, e->stream));
+    PBA_HIP(J.fe_ptr.upload(P.fe_ptr, e->stream));
+    PBA_HIP(J.fe_entries.upload(P.fe_entries, e->stream));
+    PBA_HIP(J.sky_i.upload(si, e->stream));
+    PBA_HIP(J.sky_j.upload(sj, e->stream));
+    PBA_HIP(hipStreamSynchronize(e->stream));  // (the plan's vectors die with this scope)
+    J.n_sky = P.n_sky;
+    J.first_h = P.first;
+    J.row_h = P.row;
+    const size_t nb = e->n_blocks, npt = e->n_points, np = std::max(e->n_pairs, 1);
+    J.lin_slots = (int)((nb * 8 + kBlockThreads - 1) / kBlockThreads);
+    J.pt_slots = (int)((npt + 255) / 256);
+    J.upd_slots = (int)((npt + nf + 255) / 256);
+    PBA_HIP(J.rec.resize(nb * kRec));
+    PBA_HIP(J.pair_rec.resize(np * kPairRec));
+    PBA_HIP(J.pair_ad.resize(np * kPairAd));
+    PBA_HIP(J.blk_data.resize(nb * kBlk));
+    PBA_HIP(J.pt_data.resize(npt * kPt));
+    PBA_HIP(J.inv.resize(npt));
+    PBA_HIP(J.frame_data.resize((size_t)nf * kFrame));
+    PBA_HIP(J.gmax_f.resize(nf));
+    PBA_HIP(J.gmax_p.resize(2 * (size_t)std::max(J.pt_slots, 1)));
+    PBA_HIP(J.cst.resize(2 * (size_t)nf));
+    PBA_HIP(J.S.resize(64 * (size_t)J.n_sky));
+    PBA_HIP(J.L.resize(64 * (size_t)J.n_sky));
+    PBA_HIP(J.Linv.resize(64 * (size_t)nf));
+    PBA_HIP(J.g.resize(8 * (size_t)nf));
+    PBA_HIP(J.x.resize(8 * (size_t)nf));
+    PBA_HIP(J.drho.resize(npt));
+    PBA_HIP(J.poses_new.resize(7 * (size_t)nf));
+    PBA_HIP(J.rho_new.resize(npt));
+    PBA_HIP(J.ab_new.resize(2 * (size_t)nf));
+    PBA_HIP(J.red.resize(2 * (nb / 16 + 2)));
+    PBA_HIP(J.red3.resize(4 * (size_t)J.upd_slots));
+    PBA_HIP(J.status.resize(1));
+    J.planned = true;
+    J.linearized = J.have_step = false;
+  }
+  return PBA_OK;
+}
+
+int sum_red(pba_engine* e, int slots, double* cost, double* n_valid) {
+  std::vector<double> h(2 * (size_t)slots);
+  PBA_HIP(hipMemcpyAsync(h.data(), e->joint.red.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  double c = 0.0, v = 0.0;
+  for (int i = 0; i < slots; ++i) {
+    c += h[2 * i];
+    v += h[2 * i + 1];
+  }
+  *cost = c;
+  *n_valid = v;
+  return PBA_OK;
+}
+
+int linearize_j(pba_engine* e, double* cost) {
+  JointSolve& J = e->joint;
+  const int nf = e->n_frames;
+  std::vector<uint8_t> f(2 * (size_t)nf, 0);  // the requested constants: a few bytes per keyframe, before every linearisation
+  for (int i = 0; i < nf; ++i) {
+    f[2 * i] = i < (int)e->gn.fixed_h.size() && e->gn.fixed_h[i];
+    f[2 * i + 1] = i < (int)e->aff.fixed_h.size() && e->aff.fixed_h[i];
+  }
+  PBA_HIP(J.fixed.upload(f, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  KernelArgs ka = make_kernel_args(e, e->pairs.p, e->rho.p);
+  ka.poses = e->poses.p;  // the fused-state prologue, as the public evaluations
+  ka.wg_red = J.red.p;
+  const int grid = J.lin_slots;
+  switch (e->opt.camera_model + 4 * e->interp) {
+    case 0: launch_moments_pm<0>(e, ka, J.rec.p, grid); break;
+    case 1: launch_moments_pm<1>(e, ka, J.rec.p, grid); break;
+    case 2: launch_moments_pm<2>(e, ka, J.rec.p, grid); break;
+    case 3: launch_moments_pm<3>(e, ka, J.rec.p, grid); break;
+    case 4: launch_moments_pm<4>(e, ka, J.rec.p, grid); break;
+    case 5: launch_moments_pm<5>(e, ka, J.rec.p, grid); break;
+    case 6: launch_moments_pm<6>(e, ka, J.rec.p, grid); break;
+    default: launch_moments_pm<7>(e, ka, J.rec.p, grid); break;
+  }
+  PBA_HIP(hipGetLastError());
+  if (e->n_pairs > 0)
+    joint_pair_kernel<<<e->n_pairs, 64, 0, e->stream>>>(J.rec.p, J.pair_ptr.p, J.pair_blocks.p, e->pair_host.p,
+                                                        e->pair_target.p, e->poses.p, J.pair_rec.p, J.pair_ad.p);
+  joint_block_kernel<<<(e->n_blocks + 255) / 256, 256, 0, e->stream>>>(J.rec.p, e->block_pair.p, J.pair_ad.p, e->n_blocks,
+                                                                      J.blk_data.p);
+  if (J.pt_slots > 0)
+    joint_point_kernel<<<J.pt_slots, 256, 0, e->stream>>>(J.blk_data.p, J.pt_ptr.p, J.pt_blocks.p, e->n_points, J.pt_data.p,
+                                                          J.gmax_p.p);
+  joint_frame_kernel<<<(nf + 255) / 256, 256, 0, e->stream>>>(J.pair_rec.p, J.frame_ptr.p, J.frame_pairs.p, J.fixed.p,
+                                                             e->poses.p, e->affine_state.p, nf, J.frame_data.p, J.cst.p,
+                                                             J.gmax_f.p);
+  PBA_HIP(hipGetLastError());
+  J.linearized = true;
+  J.have_step = false;
+  double c = 0.0;
+  if (int rc = sum_red(e, grid, &c, &J.n_valid)) return rc;
+  if (cost) *cost = c;
+  return PBA_OK;
+}
+
+// the gradient max norm of the linearisation (free poses, points with blocks, free (a, b))
+int gradient_norm(pba_engine* e, double* gmax) {
+  JointSolve& J = e->joint;
+  std::vector<double> f(e->n_frames), p(2 * (size_t)std::max(J.pt_slots, 1), 0.0);
+  PBA_HIP(hipMemcpyAsync(f.data(), J.gmax_f.p, sizeof(double) * f.size(), hipMemcpyDeviceToHost, e->stream));
+  if (J.pt_slots > 0)
+    PBA_HIP(hipMemcpyAsync(p.data(), J.gmax_p.p, sizeof(double) * 2 * (size_t)J.pt_slots, hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  double g = 0.0;
+  for (double v : f) g = std::max(g, v);
+  for (int s = 0; s < J.pt_slots; ++s) g = std::max(g, p[2 * s + 1]);
+  *gmax = g;
+  return PBA_OK;
+}
+
+int step_j(pba_engine* e, double lambda, double* model, int* status, double* sq_step, double* sq_x) {
+  JointSolve& J = e->joint;
+  const int nf = e->n_frames, npt = e->n_points;
+  if (npt > 0) joint_damp_kernel<<<(npt + 255) / 256, 256, 0, e->stream>>>(J.pt_data.p, npt, lambda, J.inv.p);
+  AsmArgsJ aa{J.pair_rec.p, J.blk_data.p, J.pt_data.p, J.inv.p, J.frame_data.p, J.frame_ptr.p, J.frame_pairs.p,
+              J.off_ptr.p, J.off_pairs.p, J.term_ptr.p, J.fe_ptr.p, J.fe_entries.p, J.sky_i.p, J.sky_j.p,
+              e->block_point.p, J.terms.p, J.cst.p, J.S.p, J.L.p, J.g.p, nf, J.n_sky, lambda};
+  joint_assemble_kernel<<<J.n_sky, 64, 0, e->stream>>>(aa);
+  joint_gradient_kernel<<<(8 * nf + 255) / 256, 256, 0, e->stream>>>(aa);
+  SolveArgsJ so{J.L.p, J.first.p, J.row.p, J.g.p, J.Linv.p, J.x.p, J.status.p, nf, J.colptr.p, J.colrows.p};
+  joint_solve_kernel<<<1, 256, 0, e->stream>>>(so);
+  UpdArgs ua{J.x.p, J.pt_data.p, J.blk_data.p, J.inv.p, J.frame_data.p, e->poses.p, e->rho.p, e->affine_state.p,
+             J.pt_ptr.p, J.pt_blocks.p, e->point_host_d.p, J.status.p, e->block_rec.p, J.cst.p, J.drho.p,
+             J.poses_new.p, J.rho_new.p, J.ab_new.p, J.red3.p, npt, nf, lambda};
+  joint_update_kernel<<<J.upd_slots, 256, 0, e->stream>>>(ua);
+  PBA_HIP(hipGetLastError());
+  int st = 0;
+  std::vector<double> h(4 * (size_t)J.upd_slots);
+  PBA_HIP(hipMemcpyAsync(&st, J.status.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipMemcpyAsync(h.data(), J.red3.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  double m = 0.0, ss = 0.0, xx = 0.0;
+  for (int s = 0; s < J.upd_slots; ++s) {
+    m += h[4 * s];
+    ss += h[4 * s + 1];
+    xx += h[4 * s + 2];
+  }
+  J.have_step = st == 0;
+  if (status) *status = st != 0 ? 1 : 0;
+  if (model) *model = st == 0 ? 0.5 * m : 0.0;
+  if (sq_step) *sq_step = ss;
+  if (sq_x) *sq_x = xx;
+  return PBA_OK;
+}
+
+int candidate_cost_j(pba_engine* e, double* cost, double* n_valid) {
+  JointSolve& J = e->joint;
+  int slots = 0;
+  if (int rc = launch_cost_only(e, e->pairs.p, J.rho_new.p, J.red.p, &slots, J.poses_new.p, nullptr, nullptr, J.ab_new.p))
+    return rc;
+  return sum_red(e, slots, cost, n_valid);
+}
+
+int accept_j(pba_engine* e) {
+  JointSolve& J = e->joint;
+  const size_t nf = e->n_frames;
+  PBA_HIP(hipMemcpyAsync(e->poses.p, J.poses_new.p, sizeof(double) * 7 * nf, hipMemcpyDeviceToDevice, e->stream));
+  PBA_HIP(hipMemcpyAsync(e->rho.p, J.rho_new.p, sizeof(double) * (size_t)e->n_points, hipMemcpyDeviceToDevice, e->stream));
+  PBA_HIP(hipMemcpyAsync(e->affine_state.p, J.ab_new.p, sizeof(double) * 2 * nf, hipMemcpyDeviceToDevice, e->stream));
+  J.linearized = J.have_step = false;
+  e->aff.linearized = e->aff.have_step = false;
+  e->pairs_fresh = false;
+  e->evaluated = false;
+  e->res_fresh = false;
+  return PBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pba_joint_linearize(pba_engine* e, double* cost) {
+  if (int rc = ready(e)) return rc;
+  return linearize_j(e, cost);
+}
+
+int pba_joint_system_size(pba_engine* e, int32_t* n) {
+  if (int rc = ready(e)) return rc;
+  if (!n) return fail(PBA_ERR_INVALID_ARGUMENT, "null size");
+  *n = 8 * e->n_frames;
+  return PBA_OK;
+}
+
+int pba_joint_step(pba_engine* e, double lambda, double* model_decrease, int32_t* solver_status) {
+  if (int rc = ready(e)) return rc;
+  if (!(lambda >= 0.0)) return fail(PBA_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
+  if (!e->joint.linearized) return fail(PBA_ERR_NOT_READY, "pba_joint_linearize first");
+  int st = 0;
+  const int rc = step_j(e, lambda, model_decrease, &st, nullptr, nullptr);
+  if (solver_status) *solver_status = st;
+  return rc;
+}
+
+int pba_joint_get_reduced_system(pba_engine* e, double* S_dense, double* g) {
+  if (int rc = ready(e)) return rc;
+  JointSolve& J = e->joint;
+  if (!J.linearized || !J.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
+  const int nf = e->n_frames;
+  const size_t n = 8 * (size_t)nf;
+  if (S_dense) {
+    std::vector<double> S((size_t)64 * J.n_sky);
+    PBA_HIP(hipMemcpyAsync(S.data(), J.S.p, sizeof(double) * S.size(), hipMemcpyDeviceToHost, e->stream));
+    PBA_HIP(hipStreamSynchronize(e->stream));
+    std::fill(S_dense, S_dense + n * n, 0.0);
+    for (int i = 0; i < nf; ++i)
+      for (int j = J.first_h[i]; j <= i; ++j) {
+        const double* B = &S[64 * (size_t)(J.row_h[i] + (j - J.first_h[i]))];
+        for (int r = 0; r < 8; ++r)
+          for (int c = 0; c < (i == j ? r + 1 : 8); ++c) {  // (a diagonal block's lower triangle is what is factored)
+            S_dense[(8 * i + r) * n + 8 * j + c] = B[8 * r + c];
+            S_dense[(8 * j + c) * n + 8 * i + r] = B[8 * r + c];
+          }
+      }
+  }
+  if (g) {
+    PBA_HIP(hipMemcpyAsync(g, J.g.p, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
+    PBA_HIP(hipStreamSynchronize(e->stream));
+  }
+  return PBA_OK;
+}
+
+int pba_joint_get_step(pba_engine* e, double* d_keyframes, double* d_inv_dist) {
+  if (int rc = ready(e)) return rc;
+  JointSolve& J = e->joint;
+  if (!J.linearized || !J.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
+  if (d_keyframes)
+    PBA_HIP(hipMemcpyAsync(d_keyframes, J.x.p, sizeof(double) * 8 * (size_t)e->n_frames, hipMemcpyDeviceToHost, e->stream));
+  if (d_inv_dist)
+    PBA_HIP(hipMemcpyAsync(d_inv_dist, J.drho.p, sizeof(double) * (size_t)e->n_points, hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  return PBA_OK;
+}
+
+int pba_joint_candidate_cost(pba_engine* e, double* cost) {
+  if (int rc = ready(e)) return rc;
+  if (!cost) return fail(PBA_ERR_INVALID_ARGUMENT, "null cost");
+  if (!e->joint.linearized || !e->joint.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
+  double nv = 0.0;
+  return candidate_cost_j(e, cost, &nv);
+}
+
+int pba_joint_accept(pba_engine* e) {
+  if (int rc = ready(e)) return rc;
+  if (!e->joint.linearized || !e->joint.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
+  return accept_j(e);
+}
+
+// Ceres' trust-region loop with the LM strategy (trust_region_minimizer.cc:67-136, levenberg_marquardt_strategy.cc), host
+// driven, in the order of tests tests/gn_reference.py::lm restates; norms over the free poses (ambient [q | t]), the ρ
+// of points with blocks and the free (a, b).
+int pba_solve_joint(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum) {
+  if (int rc = ready(e)) return rc;
+  pba_solver_options opt{20, 5, 1e4, 1e-6, 1e-8, 1e-3, 1e-10, 1e16, 1e-32};
+  if (o) opt = *o;
+  if (opt.max_num_consecutive_invalid_steps <= 0) opt.max_num_consecutive_invalid_steps = 5;
+  const auto t0 = std::chrono::steady_clock::now();
+  JointSolve& J = e->joint;
+  pba_solver_summary s{};
+  s.termination = PBA_TERMINATION_MAX_ITERATIONS;
+  s.stop_reason = PBA_STOP_MAX_ITERATIONS;
+  std::vector<pba_iteration_summary>& hist = e->gn.history;
+  hist.clear();
+  double cost = 0.0, gmax = 0.0;
+  if (int rc = linearize_j(e, &cost)) return rc;
+  if (int rc = gradient_norm(e, &gmax)) return rc;
+  s.initial_cost = cost;
+  double radius = opt.initial_trust_region_radius, factor = 2.0, x_norm = -1.0;
+  int invalid = 0, it = 0;
+  hist.push_back({0, 1, 1, 0, cost, 0.0, 0.0, radius, 0.0, gmax});
+  auto finish = [&](int term, int reason) {
+    s.termination = term;
+    s.stop_reason = reason;
+  };
+  if (gmax <= opt.gradient_tolerance) {
+    finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_GRADIENT_TOLERANCE);
+  } else {
+    for (it = 1; it <= opt.max_iterations; ++it) {
+      double model = 0.0, ss = 0.0, xx = 0.0, cand = 0.0, nv = 0.0;
+      int st = 0;
+      if (int rc = step_j(e, 1.0 / radius, &model, &st, &ss, &xx)) return rc;
+      if (st != 0 || !(model > 0.0)) {  // invalid step
+        if (++invalid >= opt.max_num_consecutive_invalid_steps) {
+          finish(PBA_TERMINATION_FAILURE, PBA_STOP_INVALID_STEPS);
+          --it;
+          break;
+        }
+        radius /= factor;
+        factor *= 2.0;
+        ++s.unsuccessful_steps;
+        hist.push_back({it, 0, 0, 0, cost, 0.0, 0.0, radius, 0.0, gmax});
+        if (radius <= opt.min_trust_region_radius) {
+          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_MIN_TRUST_REGION_RADIUS);
+          break;
+        }
+        continue;
+      }
+      invalid = 0;
+      const double n_valid = J.n_valid;
+      if (int rc = candidate_cost_j(e, &cand, &nv)) return rc;
+      if (nv < n_valid) cand = DBL_MAX;  // a failed evaluation (pba_solve's rule)
+      const double step = std::sqrt(ss);
+      if (step <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance)) {
+        finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_PARAMETER_TOLERANCE);
+        break;
+      }
+      if (std::fabs(cost - cand) <= opt.function_tolerance * cost) {
+        finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_FUNCTION_TOLERANCE);
+        break;
+      }
+      const double rel = (cost - cand) / model;
+      if (rel > opt.min_relative_decrease) {
+        if (int rc = accept_j(e)) return rc;
+        const double before = cost;
+        if (int rc = linearize_j(e, &cost)) return rc;  // (its cost is the candidate's: the same rows at the same state)
+        if (int rc = gradient_norm(e, &gmax)) return rc;
+        x_norm = std::sqrt(xx);
+        radius = std::min(opt.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3)));
+        factor = 2.0;
+        ++s.successful_steps;
+        hist.push_back({it, 1, 1, 0, cost, before - cost, rel, radius, step, gmax});
+        if (it < opt.max_iterations && gmax <= opt.gradient_tolerance) {
+          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_GRADIENT_TOLERANCE);
+          break;
+        }
+      } else {
+        radius /= factor;
+        factor *= 2.0;
+        ++s.unsuccessful_steps;
+        hist.push_back({it, 0, 1, 0, cand, cost - cand, rel, radius, step, gmax});
+        if (radius <= opt.min_trust_region_radius) {
+          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_MIN_TRUST_REGION_RADIUS);
+          break;
+        }
+      }
+    }
+    if (it > opt.max_iterations) it = opt.max_iterations;
+  }
+  s.iterations = it;
+  s.final_cost = cost;
+  s.gradient_max_norm = gmax;
+  s.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (sum) *sum = s;
+  return PBA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,135 @@
+// pba_joint_plan.cpp — see pba_joint_plan.h.
+#include "pba_joint_plan.h"
+
+#include <algorithm>
+
+#include "pba_gn_plan.h"
+
+namespace pba {
+namespace detail {
+
+namespace {
+
+// CSR from a count-then-fill pass: ptr from the counts in ptr[1…], then `at` as the running cursors
+void prefix(std::vector<int>& ptr) {
+  for (size_t i = 0; i + 1 < ptr.size(); ++i) ptr[i + 1] += ptr[i];
+}
+
+}  // namespace
+
+bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
+  const int nf = in.n_frames, np = in.n_pairs, npt = in.n_points, nb = in.n_blocks;
+  if (nf <= 0 || np < 0 || npt < 0 || nb < 0) return false;
+  for (int p = 0; p < np; ++p) {
+    if (in.pair_host[p] < 0 || in.pair_host[p] >= nf || in.pair_target[p] < 0 || in.pair_target[p] >= nf) return false;
+    if (in.pair_host[p] == in.pair_target[p]) return false;
+  }
+  for (int q = 0; q < npt; ++q)
+    if (in.point_host[q] < 0 || in.point_host[q] >= nf) return false;
+  for (int b = 0; b < nb; ++b) {
+    if (in.block_pair[b] < 0 || in.block_pair[b] >= np || in.block_point[b] < 0 || in.block_point[b] >= npt) return false;
+    if (in.pair_host[in.block_pair[b]] != in.point_host[in.block_point[b]]) return false;
+  }
+  // blocks of each pair and of each point (counting sorts: ascending)
+  P.pair_ptr.assign(np + 1, 0);
+  P.pt_ptr.assign(npt + 1, 0);
+  for (int b = 0; b < nb; ++b) {
+    ++P.pair_ptr[in.block_pair[b] + 1];
+    ++P.pt_ptr[in.block_point[b] + 1];
+  }
+  prefix(P.pair_ptr);
+  prefix(P.pt_ptr);
+  P.pair_blocks.resize(nb);
+  P.pt_blocks.resize(nb);
+  {
+    std::vector<int> at(P.pair_ptr.begin(), P.pair_ptr.end() - 1), aq(P.pt_ptr.begin(), P.pt_ptr.end() - 1);
+    for (int b = 0; b < nb; ++b) {
+      P.pair_blocks[at[in.block_pair[b]]++] = b;
+      P.pt_blocks[aq[in.block_point[b]]++] = b;
+    }
+  }
+  // pairs of each keyframe: as host, then as target
+  P.frame_ptr.assign(nf + 1, 0);
+  for (int p = 0; p < np; ++p) {
+    ++P.frame_ptr[in.pair_host[p] + 1];
+    ++P.frame_ptr[in.pair_target[p] + 1];
+  }
+  prefix(P.frame_ptr);
+  P.frame_pairs.resize(2 * (size_t)np);
+  {
+    std::vector<int> at(P.frame_ptr.begin(), P.frame_ptr.end() - 1);
+    for (int p = 0; p < np; ++p) P.frame_pairs[at[in.pair_host[p]]++] = 2 * p;
+    for (int p = 0; p < np; ++p) P.frame_pairs[at[in.pair_target[p]]++] = 2 * p + 1;
+  }
+  auto target_of = [&](int b) { return in.pair_target[in.block_pair[b]]; };
+  // skyline profile: every two keyframes of one point share a block of the reduced system
+  P.first.resize(nf);
+  for (int f = 0; f < nf; ++f) P.first[f] = f;
+  for (int q = 0; q < npt; ++q) {
+    if (P.pt_ptr[q] == P.pt_ptr[q + 1]) continue;
+    int lo = in.point_host[q];
+    for (int k = P.pt_ptr[q]; k < P.pt_ptr[q + 1]; ++k) lo = std::min(lo, target_of(P.pt_blocks[k]));
+    P.first[in.point_host[q]] = std::min(P.first[in.point_host[q]], lo);
+    for (int k = P.pt_ptr[q]; k < P.pt_ptr[q + 1]; ++k) {
+      const int t = target_of(P.pt_blocks[k]);
+      P.first[t] = std::min(P.first[t], lo);
+    }
+  }
+  skyline_profile(P.first, P.row, P.last, P.colptr, P.colrows);
+  P.n_sky = P.row[nf];
+  auto sky = [&](int i, int j) { return P.row[i] + (j - P.first[i]); };  // i ≥ j ≥ first[i]
+  // pairs of each off-diagonal skyline block
+  P.off_ptr.assign(P.n_sky + 1, 0);
+  auto sky_pair = [&](int p) {
+    const int h = in.pair_host[p], t = in.pair_target[p];
+    return sky(std::max(h, t), std::min(h, t));
+  };
+  for (int p = 0; p < np; ++p)
+    if (P.pair_ptr[p] < P.pair_ptr[p + 1]) ++P.off_ptr[sky_pair(p) + 1];  // (a pair without blocks lies in no point's span)
+  prefix(P.off_ptr);
+  P.off_pairs.resize(P.off_ptr[P.n_sky]);
+  {
+    std::vector<int> at(P.off_ptr.begin(), P.off_ptr.end() - 1);
+    for (int p = 0; p < np; ++p)
+      if (P.pair_ptr[p] < P.pair_ptr[p + 1])
+        P.off_pairs[at[sky_pair(p)]++] = 2 * p + (in.pair_host[p] < in.pair_target[p] ? 1 : 0);
+  }
+  // Schur terms per skyline block and entries per keyframe: two passes over the points' entries (count, fill)
+  auto frame_of = [&](int e) { return e < 0 ? in.point_host[~e] : target_of(e); };
+  P.term_ptr.assign(P.n_sky + 1, 0);
+  P.fe_ptr.assign(nf + 1, 0);
+  std::vector<int> at_t, at_f;
+  std::vector<int> ent;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int q = 0; q < npt; ++q) {
+      if (P.pt_ptr[q] == P.pt_ptr[q + 1]) continue;
+      ent.clear();
+      ent.push_back(~q);
+      for (int k = P.pt_ptr[q]; k < P.pt_ptr[q + 1]; ++k) ent.push_back(P.pt_blocks[k]);
+      for (int a : ent) {
+        const int fa = frame_of(a);
+        if (pass == 0) ++P.fe_ptr[fa + 1];
+        else P.fe_entries[at_f[fa]++] = a;
+        for (int b : ent) {
+          const int fb = frame_of(b);
+          if (fa < fb) continue;
+          const int s = sky(fa, fb);
+          if (pass == 0) ++P.term_ptr[s + 1];
+          else P.terms[at_t[s]++] = JointTerm{a, b};
+        }
+      }
+    }
+    if (pass == 0) {
+      prefix(P.term_ptr);
+      prefix(P.fe_ptr);
+      P.terms.resize(P.term_ptr[P.n_sky]);
+      P.fe_entries.resize(P.fe_ptr[nf]);
+      at_t.assign(P.term_ptr.begin(), P.term_ptr.end() - 1);
+      at_f.assign(P.fe_ptr.begin(), P.fe_ptr.end() - 1);
+    }
+  }
+  return true;
+}
+
+}  // namespace detail
+}  // namespace pba

@@ -1,0 +1,51 @@
+// pba_joint_plan.h — the host-only plan of the joint solve of poses, inverse distances and brightness (pba_joint.hip):
+// which blocks, pairs, points and Schur terms each sum of the reduced system runs over, in a fixed order, and the
+// system's profile.  No device code, no engine: plain vectors in, plain vectors out (tests/cpp/joint_plan_check.cpp
+// checks it stand-alone, under the sanitizers).
+#pragma once
+
+#include <vector>
+
+namespace pba {
+namespace detail {
+
+struct JointPlanInput {
+  int n_frames = 0, n_pairs = 0, n_points = 0, n_blocks = 0;
+  const int* pair_host = nullptr;    // per pair
+  const int* pair_target = nullptr;  // per pair
+  const int* block_pair = nullptr;   // per block
+  const int* block_point = nullptr;  // per block
+  const int* point_host = nullptr;   // per point
+};
+
+// An ENTRY is one 8-vector W = Σ w J_kfᵀ J_ρ of a point p: e ≥ 0 is block e's target part W_t (its keyframe: the
+// block's target), e < 0 the point ~e's host part W_h summed over its blocks (its keyframe: the point's host).  A
+// point's entries in order: the host part, then its blocks ascending.
+struct JointTerm {
+  int a, b;  // entries of one point: −W_a W_bᵀ / H'_ρρ goes into the block (keyframe of a, keyframe of b)
+};
+
+// The reduced system is 8·n_frames square, 8×8 blocks, lower skyline by block rows: row i holds the blocks (i, j),
+// first[i] ≤ j ≤ i, at block offsets row[i] + (j − first[i]).  first[i] is the smallest keyframe that shares a point
+// with i (as host or target of one of the point's blocks): the pose system's profile (skyline_profile of
+// pba_gn_plan.h), with the point elimination's fill and loop closures.
+struct JointPlan {
+  std::vector<int> pair_ptr, pair_blocks;    // CSR: the blocks of each pair, ascending
+  std::vector<int> frame_ptr, frame_pairs;   // CSR: per keyframe, pair · 2 + role (0: host, 1: target), hosts' pairs
+                                             // first, each ascending
+  std::vector<int> pt_ptr, pt_blocks;        // CSR: the blocks of each point, ascending
+  std::vector<int> first, row, last, colptr, colrows;  // skyline_profile (row has n_frames + 1 entries)
+  std::vector<int> off_ptr, off_pairs;       // CSR per skyline block (the diagonal ones stay empty): pair · 2 + t,
+                                             // t = 1 when the pair's host is the block's column (H_htᵀ goes in)
+  std::vector<int> term_ptr;                 // CSR per skyline block: its Schur terms, points ascending, then a, then b
+  std::vector<JointTerm> terms;              //   in the point's entry order (block (i, j): keyframe(a) = i, keyframe(b) = j)
+  std::vector<int> fe_ptr, fe_entries;       // CSR per keyframe: the entries on it, points ascending
+  int n_sky = 0;                             // skyline blocks
+};
+
+// false when an index is out of range, a block's pair does not have its point's host as host, or a pair's target is
+// its host (the plan is then unspecified)
+bool build_joint_plan(const JointPlanInput& in, JointPlan& P);
+
+}  // namespace detail
+}  // namespace pba

@@ -248,6 +248,7 @@ int pba_set_level(pba_engine* e, int32_t level) {
   e->level = level;
   e->pairs_fresh = false;
   e->evaluated = false;
+  e->joint.linearized = false;
   if (e->opt_intr) return upload_intrinsics_state(e);  // the intrinsics state's image at this level
   return PBA_OK;
 }

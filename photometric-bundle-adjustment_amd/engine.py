@@ -205,6 +205,14 @@ def lib(path: Optional[str] = None):
         "pba_affine_candidate_cost": ([vp, C.POINTER(C.c_double)], C.c_int),
         "pba_affine_accept": ([vp], C.c_int),
         "pba_solve_affine": ([vp, C.POINTER(SolverOptions), C.POINTER(SolverSummary)], C.c_int),
+        "pba_joint_linearize": ([vp, C.POINTER(C.c_double)], C.c_int),
+        "pba_joint_system_size": ([vp, C.POINTER(i32)], C.c_int),
+        "pba_joint_step": ([vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i32)], C.c_int),
+        "pba_joint_get_reduced_system": ([vp, vp, vp], C.c_int),
+        "pba_joint_get_step": ([vp, vp, vp], C.c_int),
+        "pba_joint_candidate_cost": ([vp, C.POINTER(C.c_double)], C.c_int),
+        "pba_joint_accept": ([vp], C.c_int),
+        "pba_solve_joint": ([vp, C.POINTER(SolverOptions), C.POINTER(SolverSummary)], C.c_int),
         "pba_gn_system_size": ([vp, C.POINTER(i32)], C.c_int),
         "pba_gn_set_rank": ([vp, i32], C.c_int),
         "pba_compute_projections": ([vp, i32, vp, vp, vp, vp, C.POINTER(OutlierThresholds), vp, vp, vp, vp], C.c_int),
@@ -666,6 +674,53 @@ class Engine:
         o = solver_options(**options)
         s = SolverSummary()
         self._ck(self._L.pba_solve_affine(self._h, C.byref(o), C.byref(s)), "pba_solve_affine")
+        return s.as_dict()
+
+    # -- the joint solve of poses, inverse distances and (a, b) (pba_joint.hip) --------------------------
+    def joint_linearize(self) -> float:
+        c = C.c_double()
+        self._ck(self._L.pba_joint_linearize(self._h, C.byref(c)), "pba_joint_linearize")
+        return c.value
+
+    def joint_system_size(self) -> int:
+        n = C.c_int32()
+        self._ck(self._L.pba_joint_system_size(self._h, C.byref(n)), "pba_joint_system_size")
+        return n.value
+
+    def joint_step(self, lam: float):
+        """(model decrease, solver status)"""
+        m, st = C.c_double(), C.c_int32()
+        self._ck(self._L.pba_joint_step(self._h, lam, C.byref(m), C.byref(st)), "pba_joint_step")
+        return m.value, st.value
+
+    def joint_get_reduced_system(self):
+        """(S (8·n_frames square, the last step's: damped, constants as identity rows), g_S); unknowns per keyframe
+        [δpose (6) | δa δb]."""
+        n = self.joint_system_size()
+        S, g = np.empty((n, n), np.float64), np.empty(n, np.float64)
+        self._ck(self._L.pba_joint_get_reduced_system(self._h, _p(S), _p(g)), "pba_joint_get_reduced_system")
+        return S, g
+
+    def joint_get_step(self):
+        """(δ of the keyframes (n_frames, 8), δρ (n_points,)) of the last step."""
+        dk, dr = np.empty((self.n_frames, 8), np.float64), np.empty(self.n_points, np.float64)
+        self._ck(self._L.pba_joint_get_step(self._h, _p(dk), _p(dr)), "pba_joint_get_step")
+        return dk, dr
+
+    def joint_candidate_cost(self) -> float:
+        c = C.c_double()
+        self._ck(self._L.pba_joint_candidate_cost(self._h, C.byref(c)), "pba_joint_candidate_cost")
+        return c.value
+
+    def joint_accept(self):
+        """poses, inverse distances and affine state ← candidate"""
+        self._ck(self._L.pba_joint_accept(self._h), "pba_joint_accept")
+
+    def solve_joint(self, **options) -> dict:
+        """pba_solve_joint; options as solver_options()."""
+        o = solver_options(**options)
+        s = SolverSummary()
+        self._ck(self._L.pba_solve_joint(self._h, C.byref(o), C.byref(s)), "pba_solve_joint")
         return s.as_dict()
 
     def set_affine_state(self, ab: np.ndarray):
