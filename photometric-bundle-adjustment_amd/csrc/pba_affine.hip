@@ -14,11 +14,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <vector>
 
 #include "pba_affine_plan.h"
+#include "pba_host_lm.h"
 #include "pba_internal.h"
 
 using namespace pba;
@@ -324,11 +324,6 @@ __global__ __launch_bounds__(64) void affine_factor_kernel(const FactorArgs a) {
   }
 }
 
-template <int PM>
-void launch_moments_pm(pba_engine* e, const KernelArgs& ka, double* rec, int grid) {
-  affine_moments_kernel<PM><<<grid, kBlockThreads, 0, e->stream>>>(ka, rec, (e->P + 7) / 8);
-}
-
 int ready(pba_engine* e) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
   if (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC || !e->affine)
@@ -383,32 +378,15 @@ int ready(pba_engine* e) {
   return PBA_OK;
 }
 
-int sum_red(pba_engine* e, int slots, double* cost) {
-  std::vector<double> h(2 * (size_t)slots);
-  PBA_HIP(hipMemcpyAsync(h.data(), e->aff.red.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
-  PBA_HIP(hipStreamSynchronize(e->stream));
-  double c = 0.0;
-  for (int i = 0; i < slots; ++i) c += h[2 * i];
-  *cost = c;
-  return PBA_OK;
-}
-
 int linearize_ab(pba_engine* e, double* cost) {
   AffineSolve& A = e->aff;
   KernelArgs ka = make_kernel_args(e, e->pairs.p, e->rho.p);
   ka.poses = e->poses.p;  // the fused-state prologue, as the public evaluations
   ka.wg_red = A.red.p;
   const int grid = (int)(((long long)e->n_blocks * 8 + kBlockThreads - 1) / kBlockThreads);
-  switch (e->opt.camera_model + 4 * e->interp) {
-    case 0: launch_moments_pm<0>(e, ka, A.rec.p, grid); break;
-    case 1: launch_moments_pm<1>(e, ka, A.rec.p, grid); break;
-    case 2: launch_moments_pm<2>(e, ka, A.rec.p, grid); break;
-    case 3: launch_moments_pm<3>(e, ka, A.rec.p, grid); break;
-    case 4: launch_moments_pm<4>(e, ka, A.rec.p, grid); break;
-    case 5: launch_moments_pm<5>(e, ka, A.rec.p, grid); break;
-    case 6: launch_moments_pm<6>(e, ka, A.rec.p, grid); break;
-    default: launch_moments_pm<7>(e, ka, A.rec.p, grid); break;
-  }
+  dispatch_pm(e, [&](auto pm) {
+    affine_moments_kernel<decltype(pm)::value><<<grid, kBlockThreads, 0, e->stream>>>(ka, A.rec.p, (e->P + 7) / 8);
+  });
   PBA_HIP(hipGetLastError());
   if (e->n_pairs > 0)
     affine_pair_kernel<<<(e->n_pairs + 255) / 256, 256, 0, e->stream>>>(A.rec.p, A.pair_ptr.p, A.pair_blocks.p, (double)e->P,
@@ -420,7 +398,7 @@ int linearize_ab(pba_engine* e, double* cost) {
   A.linearized = true;
   A.have_step = false;
   double c = 0.0;
-  if (int rc = sum_red(e, grid, &c)) return rc;
+  if (int rc = sum_red(e, A.red.p, grid, &c, nullptr)) return rc;
   if (cost) *cost = c;
   return PBA_OK;
 }
@@ -449,7 +427,7 @@ int candidate_cost_ab(pba_engine* e, double* cost) {
   int slots = 0;
   if (int rc = launch_cost_only(e, e->pairs.p, e->rho.p, e->aff.red.p, &slots, e->poses.p, nullptr, nullptr, e->aff.ab_new.p))
     return rc;
-  return sum_red(e, slots, cost);
+  return sum_red(e, e->aff.red.p, slots, cost, nullptr);
 }
 
 int accept_ab(pba_engine* e) {
@@ -530,20 +508,10 @@ int pba_affine_get_system(pba_engine* e, double* H_dense, double* g) {
   std::vector<uint8_t> cst(nf);
   for (int i = 0; i < nf; ++i)
     cst[i] = (i < (int)A.fixed_h.size() && A.fixed_h[i]) || !(S[4 * (size_t)(A.row_h[i] + (i - A.first_h[i])) + 3] > 0.0);
-  if (H_dense) {
-    std::fill(H_dense, H_dense + n * n, 0.0);
-    for (int i = 0; i < nf; ++i)
-      for (int j = A.first_h[i]; j <= i; ++j) {
-        const double* B = &S[4 * (size_t)(A.row_h[i] + (j - A.first_h[i]))];
-        for (int r = 0; r < 2; ++r)
-          for (int c = 0; c < 2; ++c) {
-            double v = B[2 * r + c];
-            if (cst[i] || cst[j]) v = i == j && r == c ? 1.0 : 0.0;
-            H_dense[(2 * i + r) * n + 2 * j + c] = v;
-            H_dense[(2 * j + c) * n + 2 * i + r] = v;
-          }
-      }
-  }
+  if (H_dense)  // (identity rows and columns for the constant keyframes)
+    skyline_to_dense<2>(S, A.first_h, A.row_h, nf, false, [&](int i, int j, int r, int c, double v) {
+      return cst[i] || cst[j] ? (i == j && r == c ? 1.0 : 0.0) : v;
+    }, H_dense);
   if (g)
     for (size_t i = 0; i < n; ++i) g[i] = cst[i / 2] ? 0.0 : gh[i];
   return PBA_OK;
@@ -581,98 +549,20 @@ int pba_affine_accept(pba_engine* e) {
   return accept_ab(e);
 }
 
-// Ceres' trust-region loop with the LM strategy (trust_region_minimizer.cc:67-136, levenberg_marquardt_strategy.cc), host
-// driven, in the order of tests tests/gn_reference.py::lm restates; norms over the free (a, b).
+// The host-driven trust-region loop (pba_host_lm.h); norms over the free (a, b).
 int pba_solve_affine(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum) {
   if (int rc = ready(e)) return rc;
-  pba_solver_options opt{20, 5, 1e4, 1e-6, 1e-8, 1e-3, 1e-10, 1e16, 1e-32};
-  if (o) opt = *o;
-  if (opt.max_num_consecutive_invalid_steps <= 0) opt.max_num_consecutive_invalid_steps = 5;
-  const auto t0 = std::chrono::steady_clock::now();
-  pba_solver_summary s{};
-  s.termination = PBA_TERMINATION_MAX_ITERATIONS;
-  s.stop_reason = PBA_STOP_MAX_ITERATIONS;
-  std::vector<pba_iteration_summary>& hist = e->gn.history;
-  hist.clear();
-  double cost = 0.0, gmax = 0.0, xnorm_now = 0.0;
-  if (int rc = linearize_ab(e, &cost)) return rc;
-  if (int rc = free_norms(e, &gmax, &xnorm_now)) return rc;
-  s.initial_cost = cost;
-  double radius = opt.initial_trust_region_radius, factor = 2.0, x_norm = -1.0;
-  int invalid = 0, it = 0;
-  hist.push_back({0, 1, 1, 0, cost, 0.0, 0.0, radius, 0.0, gmax});
-  auto finish = [&](int term, int reason) {
-    s.termination = term;
-    s.stop_reason = reason;
-  };
-  if (gmax <= opt.gradient_tolerance) {
-    finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_GRADIENT_TOLERANCE);
-  } else {
-    for (it = 1; it <= opt.max_iterations; ++it) {
-      double model = 0.0, mx = 0.0, dd = 0.0, cand = 0.0;
-      int st = 0;
-      if (int rc = step_ab(e, 1.0 / radius, &model, &st, &mx, &dd)) return rc;
-      if (st != 0 || !(model > 0.0)) {  // invalid step
-        if (++invalid >= opt.max_num_consecutive_invalid_steps) {
-          finish(PBA_TERMINATION_FAILURE, PBA_STOP_INVALID_STEPS);
-          --it;
-          break;
-        }
-        radius /= factor;
-        factor *= 2.0;
-        ++s.unsuccessful_steps;
-        hist.push_back({it, 0, 0, 0, cost, 0.0, 0.0, radius, 0.0, gmax});
-        if (radius <= opt.min_trust_region_radius) {
-          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_MIN_TRUST_REGION_RADIUS);
-          break;
-        }
-        continue;
-      }
-      invalid = 0;
-      if (int rc = candidate_cost_ab(e, &cand)) return rc;
-      const double step = std::sqrt(dd);
-      if (step <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance)) {
-        finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_PARAMETER_TOLERANCE);
-        break;
-      }
-      if (std::fabs(cost - cand) <= opt.function_tolerance * cost) {
-        finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_FUNCTION_TOLERANCE);
-        break;
-      }
-      const double rel = (cost - cand) / model;
-      if (rel > opt.min_relative_decrease) {
-        if (int rc = accept_ab(e)) return rc;
-        const double before = cost;
-        if (int rc = linearize_ab(e, &cost)) return rc;  // (its cost is the candidate's: the same rows at the same state)
-        if (int rc = free_norms(e, &gmax, &xnorm_now)) return rc;
-        x_norm = xnorm_now;
-        radius = std::min(opt.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3)));
-        factor = 2.0;
-        ++s.successful_steps;
-        hist.push_back({it, 1, 1, 0, cost, before - cost, rel, radius, step, gmax});
-        if (it < opt.max_iterations && gmax <= opt.gradient_tolerance) {
-          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_GRADIENT_TOLERANCE);
-          break;
-        }
-      } else {
-        radius /= factor;
-        factor *= 2.0;
-        ++s.unsuccessful_steps;
-        hist.push_back({it, 0, 1, 0, cand, cost - cand, rel, radius, step, gmax});
-        if (radius <= opt.min_trust_region_radius) {
-          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_MIN_TRUST_REGION_RADIUS);
-          break;
-        }
-      }
-    }
-    if (it > opt.max_iterations) it = opt.max_iterations;
-  }
-  s.iterations = it;
-  s.final_cost = cost;
-  s.gradient_max_norm = gmax;
-  s.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (sum) *sum = s;
-  return PBA_OK;
+  HostLmStages stages{
+      [&](double* cost, double* gmax, double* x_norm) {
+        if (int rc = linearize_ab(e, cost)) return rc;
+        return free_norms(e, gmax, x_norm);
+      },
+      [&](double lambda, int* status, double* model, double* sq_step) {
+        return step_ab(e, lambda, model, status, nullptr, sq_step);
+      },
+      [&](double* cost) { return candidate_cost_ab(e, cost); },
+      [&]() { return accept_ab(e); }};
+  return host_lm(o, stages, e->gn.history, sum);
 }
 
 }  // extern "C"

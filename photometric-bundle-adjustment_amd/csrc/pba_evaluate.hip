@@ -520,16 +520,7 @@ void launch_mode(pba_engine* e, const KernelArgs& ka, int mode) {
     }
     return;
   }
-  switch (e->opt.camera_model + 4 * e->interp) {
-    case 0: launch_photometric<0>(e, ka, mode); break;
-    case 1: launch_photometric<1>(e, ka, mode); break;
-    case 2: launch_photometric<2>(e, ka, mode); break;
-    case 3: launch_photometric<3>(e, ka, mode); break;
-    case 4: launch_photometric<4>(e, ka, mode); break;
-    case 5: launch_photometric<5>(e, ka, mode); break;
-    case 6: launch_photometric<6>(e, ka, mode); break;
-    default: launch_photometric<7>(e, ka, mode); break;
-  }
+  dispatch_pm(e, [&](auto pm) { launch_photometric<decltype(pm)::value>(e, ka, mode); });
 }
 
 KernelArgs make_kernel_args(pba_engine* e, const PairRec* pairs, const double* rho) {

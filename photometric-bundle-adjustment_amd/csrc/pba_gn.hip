@@ -755,79 +755,8 @@ __global__ void import_sky_kernel(const ImportSkyArgs a, double lambda, const do
 }
 
 // ------------------------------------------------------------------------------------------------
-// Updates: poses T·exp(δ) (se3.hpp:763-784) and back-substituted inverse distances
+// Updates: poses T·exp(δ) (se3_exp_mul, pba_internal.h) and back-substituted inverse distances
 // ------------------------------------------------------------------------------------------------
-__device__ void se3_exp_mul(const double* T, const double* d, double* out) {
-  const double w0 = d[3], w1 = d[4], w2 = d[5];
-  const double th2 = w0 * w0 + w1 * w1 + w2 * w2, th = sqrt(th2);
-  double imag, real, A, B;
-  if (th < 1e-10) {
-    real = 1.0 - th2 / 8.0 + th2 * th2 / 384.0;
-    imag = 0.5 - th2 / 48.0 + th2 * th2 / 3840.0;
-    A = 0.5;
-    B = 1.0 / 6.0;
-  } else {
-    // one sincos of θ/2 (sin θ = 2 sc, 1 − cos θ = 2 s², the latter without cancellation) and one reciprocal of θ
-    // instead of two sincos and three IEEE divisions: the candidate poses' fp64 chain is the update kernel's latency
-    double sh, ch;
-    sincos(0.5 * th, &sh, &ch);
-    const double it = rcp_nr(th);
-    real = ch;
-    imag = sh * it;
-    A = 2.0 * imag * imag;
-    B = (th - 2.0 * sh * ch) * (it * it * it);
-  }
-  const double qx = imag * w0, qy = imag * w1, qz = imag * w2, qw = real;
-  // V υ = υ + A ω×υ + B ω×(ω×υ)
-  const double v0 = d[0], v1 = d[1], v2 = d[2];
-  const double c0 = w1 * v2 - w2 * v1, c1 = w2 * v0 - w0 * v2, c2 = w0 * v1 - w1 * v0;
-  const double cc0 = w1 * c2 - w2 * c1, cc1 = w2 * c0 - w0 * c2, cc2 = w0 * c1 - w1 * c0;
-  const double tx = v0 + A * c0 + B * cc0, ty = v1 + A * c1 + B * cc1, tz = v2 + A * c2 + B * cc2;
-  // T · exp(δ): q = q_T ⊗ q_δ (normalised), t = t_T + R_T t_δ
-  const double ax = T[0], ay = T[1], az = T[2], aw = T[3];
-  double rw = aw * qw - ax * qx - ay * qy - az * qz;
-  double rx = aw * qx + ax * qw + ay * qz - az * qy;
-  double ry = aw * qy + ay * qw + az * qx - ax * qz;
-  double rz = aw * qz + az * qw + ax * qy - ay * qx;
-  const double n = rsqrt_nr(rw * rw + rx * rx + ry * ry + rz * rz);  // (|q| ≈ 1: the seed + correction is ~1 ulp)
-  double u0 = ay * tz - az * ty, u1 = az * tx - ax * tz, u2 = ax * ty - ay * tx;
-  u0 += u0; u1 += u1; u2 += u2;
-  out[0] = rx * n; out[1] = ry * n; out[2] = rz * n; out[3] = rw * n;
-  out[4] = T[4] + tx + aw * u0 + (ay * u2 - az * u1);
-  out[5] = T[5] + ty + aw * u1 + (az * u0 - ax * u2);
-  out[6] = T[6] + tz + aw * u2 + (ax * u1 - ay * u0);
-}
-
-
-// Σ over the workgroup of N per-lane values and the max of one more, in a fixed order (xor butterflies in each wave,
-// then the waves in order, as wg_reduce2): thread q < N stores sum q to *out[q], thread N the max to *out_max.  Every
-// thread must call it.
-template <int N>
-__device__ __forceinline__ void wg_reduce_sum_max(double (&v)[N], double m, double* const (&out)[N], double* out_max) {
-  __shared__ double s[N + 1][16];
-  for (int o = 32; o >= 1; o >>= 1) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) v[q] += __shfl_xor(v[q], o, 64);
-    m = fmax(m, __shfl_xor(m, o, 64));
-  }
-  const int w = threadIdx.x / 64, l = threadIdx.x % 64;
-  if (l == 0) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) s[q][w] = v[q];
-    s[N][w] = m;
-  }
-  __syncthreads();
-  if (threadIdx.x <= N) {  // one thread per sum, the waves in order
-    const int q = threadIdx.x, nw = (int)(blockDim.x / 64);
-    double x = 0.0;
-    for (int i = 0; i < nw; ++i) x = q < N ? x + s[q][i] : fmax(x, s[N][i]);
-    double* dst = out_max;
-#pragma unroll
-    for (int k = 0; k < N; ++k) dst = q == k ? out[k] : dst;
-    *dst = x;
-  }
-}
-
 // The update workgroups' partials besides the model decrease (slot layout of red): Σ|x − x_new|² and Σ|x_new|² in the
 // ambient parameter space (red2, two doubles per slot: Ceres' step_norm and x_norm, trust_region_minimizer.cc:706-726,
 // :813-814) and max |x − (x ⊞ −g)| at the current state (gmax, one double per slot: gradient_max_norm,

@@ -867,13 +867,8 @@ void launch_intr_accept(pba_engine* e, const double* lm) {
                                                G.nc_sys);
 }
 
-// The photometric producer at the engine's state: the state's poses and inverse distances, the intrinsics state for the
-// target projection (make_kernel_args), the active level's images.
-template <int PM>
-static void launch_intr_rows_photometric(pba_engine* e, const KernelArgs& ka, const IntrMomArgs& ma) {
-  intr_rows_photometric_kernel<PM><<<(ma.n + 31) / 32, 256, 0, e->stream>>>(ka, ma);
-}
-
+// The photometric producer runs at the engine's state: the state's poses and inverse distances, the intrinsics state for
+// the target projection (make_kernel_args), the active level's images.
 void enqueue_intr_rows(pba_engine* e, const double* lm, bool accept) {
   GnData& G = e->gn;
   if (lm && accept) launch_intr_accept(e, lm);
@@ -881,16 +876,9 @@ void enqueue_intr_rows(pba_engine* e, const double* lm, bool accept) {
     KernelArgs ka = make_kernel_args(e, nullptr, e->rho.p);
     ka.poses = e->poses.p;
     const IntrMomArgs ma{G.ib_rec.p, G.ib_data.p, e->n_blocks, lm ? lm : G.lm_idle.p};
-    switch (e->opt.camera_model + 4 * e->interp) {  // PM = camera model + 4 · interpolator
-      case 0: launch_intr_rows_photometric<0>(e, ka, ma); break;
-      case 1: launch_intr_rows_photometric<1>(e, ka, ma); break;
-      case 2: launch_intr_rows_photometric<2>(e, ka, ma); break;
-      case 3: launch_intr_rows_photometric<3>(e, ka, ma); break;
-      case 4: launch_intr_rows_photometric<4>(e, ka, ma); break;
-      case 5: launch_intr_rows_photometric<5>(e, ka, ma); break;
-      case 6: launch_intr_rows_photometric<6>(e, ka, ma); break;
-      default: launch_intr_rows_photometric<7>(e, ka, ma); break;
-    }
+    dispatch_pm(e, [&](auto pm) {
+      intr_rows_photometric_kernel<decltype(pm)::value><<<(ma.n + 31) / 32, 256, 0, e->stream>>>(ka, ma);
+    });
     return;
   }
   IntrRowsArgs ra{G.ib_rec.p, e->poses.p, e->rho.p, e->u_ref.p, e->u_obs.p, e->frame_cam.p, e->intr_d.p,

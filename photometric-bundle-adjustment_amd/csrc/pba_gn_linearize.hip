@@ -723,16 +723,7 @@ namespace pba {
 namespace detail {
 
 void launch_linearize_photometric(pba_engine* e, const KernelArgs& ka, const LinArgs& la) {
-  switch (e->opt.camera_model + 4 * e->interp) {
-    case 0: launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, 0>(e, ka, la); break;
-    case 1: launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, 1>(e, ka, la); break;
-    case 2: launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, 2>(e, ka, la); break;
-    case 3: launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, 3>(e, ka, la); break;
-    case 4: launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, 4>(e, ka, la); break;
-    case 5: launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, 5>(e, ka, la); break;
-    case 6: launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, 6>(e, ka, la); break;
-    default: launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, 7>(e, ka, la); break;
-  }
+  dispatch_pm(e, [&](auto pm) { launch_linearize<PBA_RESIDUAL_PHOTOMETRIC, decltype(pm)::value>(e, ka, la); });
 }
 
 void launch_linearize_geometric(pba_engine* e, const KernelArgs& ka, const LinArgs& la) {

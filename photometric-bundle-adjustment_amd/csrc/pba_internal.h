@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
@@ -94,6 +95,48 @@ __device__ __forceinline__ void pair_translation(const double* __restrict__ H, c
     r.t[j] = tt[j];
     r.tf[j] = (float)tt[j];
   }
+}
+// The pose update T·exp(δ) (se3.hpp:763-784), T and out as [q | t], δ = [υ | ω]: the candidate poses and Plus(x, −g) of
+// the gradient norm, in pba_gn.hip and pba_joint.hip.
+__device__ inline void se3_exp_mul(const double* T, const double* d, double* out) {
+  const double w0 = d[3], w1 = d[4], w2 = d[5];
+  const double th2 = w0 * w0 + w1 * w1 + w2 * w2, th = sqrt(th2);
+  double imag, real, A, B;
+  if (th < 1e-10) {
+    real = 1.0 - th2 / 8.0 + th2 * th2 / 384.0;
+    imag = 0.5 - th2 / 48.0 + th2 * th2 / 3840.0;
+    A = 0.5;
+    B = 1.0 / 6.0;
+  } else {
+    // one sincos of θ/2 (sin θ = 2 sc, 1 − cos θ = 2 s², the latter without cancellation) and one reciprocal of θ
+    // instead of two sincos and three IEEE divisions: the candidate poses' fp64 chain is the update kernel's latency
+    double sh, ch;
+    sincos(0.5 * th, &sh, &ch);
+    const double it = rcp_nr(th);
+    real = ch;
+    imag = sh * it;
+    A = 2.0 * imag * imag;
+    B = (th - 2.0 * sh * ch) * (it * it * it);
+  }
+  const double qx = imag * w0, qy = imag * w1, qz = imag * w2, qw = real;
+  // V υ = υ + A ω×υ + B ω×(ω×υ)
+  const double v0 = d[0], v1 = d[1], v2 = d[2];
+  const double c0 = w1 * v2 - w2 * v1, c1 = w2 * v0 - w0 * v2, c2 = w0 * v1 - w1 * v0;
+  const double cc0 = w1 * c2 - w2 * c1, cc1 = w2 * c0 - w0 * c2, cc2 = w0 * c1 - w1 * c0;
+  const double tx = v0 + A * c0 + B * cc0, ty = v1 + A * c1 + B * cc1, tz = v2 + A * c2 + B * cc2;
+  // T · exp(δ): q = q_T ⊗ q_δ (normalised), t = t_T + R_T t_δ
+  const double ax = T[0], ay = T[1], az = T[2], aw = T[3];
+  double rw = aw * qw - ax * qx - ay * qy - az * qz;
+  double rx = aw * qx + ax * qw + ay * qz - az * qy;
+  double ry = aw * qy + ay * qw + az * qx - ax * qz;
+  double rz = aw * qz + az * qw + ax * qy - ay * qx;
+  const double n = rsqrt_nr(rw * rw + rx * rx + ry * ry + rz * rz);  // (|q| ≈ 1: the seed + correction is ~1 ulp)
+  double u0 = ay * tz - az * ty, u1 = az * tx - ax * tz, u2 = ax * ty - ay * tx;
+  u0 += u0; u1 += u1; u2 += u2;
+  out[0] = rx * n; out[1] = ry * n; out[2] = rz * n; out[3] = rw * n;
+  out[4] = T[4] + tx + aw * u0 + (ay * u2 - az * u1);
+  out[5] = T[5] + ty + aw * u1 + (az * u0 - ax * u2);
+  out[6] = T[6] + tz + aw * u2 + (ax * u1 - ay * u0);
 }
 // fp32 projection constants of the Jacobian chain from the fp64 projection layout (cx, cy unused there)
 __device__ __forceinline__ void camera_kf(const double* __restrict__ tk, float* kf) {
@@ -259,6 +302,35 @@ __device__ __forceinline__ void wg_reduce2(double a, double b, double* out) {
     for (int i = 0; i < (int)(blockDim.x / 64); ++i) { x += sa[i]; y += sb[i]; }
     out[0] = x;
     out[1] = y;
+  }
+}
+
+// Σ over the workgroup of N per-lane values and the max of one more, in a fixed order (xor butterflies in each wave,
+// then the waves in order, as wg_reduce2): thread q < N stores sum q to *out[q], thread N the max to *out_max.  Every
+// thread must call it.
+template <int N>
+__device__ __forceinline__ void wg_reduce_sum_max(double (&v)[N], double m, double* const (&out)[N], double* out_max) {
+  __shared__ double s[N + 1][16];
+  for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) v[q] += __shfl_xor(v[q], o, 64);
+    m = fmax(m, __shfl_xor(m, o, 64));
+  }
+  const int w = threadIdx.x / 64, l = threadIdx.x % 64;
+  if (l == 0) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) s[q][w] = v[q];
+    s[N][w] = m;
+  }
+  __syncthreads();
+  if (threadIdx.x <= N) {  // one thread per sum, the waves in order
+    const int q = threadIdx.x, nw = (int)(blockDim.x / 64);
+    double x = 0.0;
+    for (int i = 0; i < nw; ++i) x = q < N ? x + s[q][i] : fmax(x, s[N][i]);
+    double* dst = out_max;
+#pragma unroll
+    for (int k = 0; k < N; ++k) dst = q == k ? out[k] : dst;
+    *dst = x;
   }
 }
 
@@ -1020,6 +1092,58 @@ namespace detail {
 inline int check_device(pba_engine* e) {
   PBA_HIP(hipSetDevice(e->opt.device));
   return PBA_OK;
+}
+
+// The photometric kernels' template parameter PM = camera model + 4 · interpolator (pba_device.h) from the engine's
+// options: calls fn(std::integral_constant<int, PM>{}).
+template <class F>
+void dispatch_pm(const pba_engine* e, F&& fn) {
+  switch (e->opt.camera_model + 4 * e->interp) {
+    case 0: fn(std::integral_constant<int, 0>{}); break;
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 3: fn(std::integral_constant<int, 3>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    case 5: fn(std::integral_constant<int, 5>{}); break;
+    case 6: fn(std::integral_constant<int, 6>{}); break;
+    default: fn(std::integral_constant<int, 7>{}); break;
+  }
+}
+
+// One workgroup-partial buffer of (Σ cost, Σ valid) pairs (wg_reduce2's slots) summed on the host, the slots in order;
+// n_valid may be null.  (static: the library's exported symbols stay the C ABI's and the units' own.)
+static inline int sum_red(pba_engine* e, const double* red, int slots, double* cost, double* n_valid) {
+  std::vector<double> h(2 * (size_t)slots);
+  PBA_HIP(hipMemcpyAsync(h.data(), red, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  double c = 0.0, v = 0.0;
+  for (int i = 0; i < slots; ++i) {
+    c += h[2 * i];
+    v += h[2 * i + 1];
+  }
+  *cost = c;
+  if (n_valid) *n_valid = v;
+  return PBA_OK;
+}
+
+// The lower block skyline S (N×N blocks row-major; row i holds the blocks (i, j), first[i] ≤ j ≤ i, at row[i] +
+// (j − first[i])) as the dense symmetric n_frames·N square matrix: at(i, j, r, c, v) is the value that goes to
+// (N·i + r, N·j + c) and its mirror for the skyline's v.  lower_diagonal: of a diagonal block only c ≤ r is read.
+template <int N, class At>
+void skyline_to_dense(const std::vector<double>& S, const std::vector<int>& first, const std::vector<int>& row,
+                      int n_frames, bool lower_diagonal, At&& at, double* dense) {
+  const size_t n = (size_t)N * n_frames;
+  std::fill(dense, dense + n * n, 0.0);
+  for (int i = 0; i < n_frames; ++i)
+    for (int j = first[i]; j <= i; ++j) {
+      const double* B = &S[(size_t)N * N * (row[i] + (j - first[i]))];
+      for (int r = 0; r < N; ++r)
+        for (int c = 0; c < (lower_diagonal && i == j ? r + 1 : N); ++c) {
+          const double v = at(i, j, r, c, B[N * r + c]);
+          dense[(N * i + r) * n + N * j + c] = v;
+          dense[(N * j + c) * n + N * i + r] = v;
+        }
+    }
 }
 
 // Kernel arguments describing the engine's current problem and state (pba_evaluate.hip, as the three launches below).

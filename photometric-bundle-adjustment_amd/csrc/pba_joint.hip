@@ -24,11 +24,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cfloat>
 #include <cmath>
 #include <vector>
 
+#include "pba_host_lm.h"
 #include "pba_internal.h"
 #include "pba_joint_plan.h"
 
@@ -255,36 +255,6 @@ __global__ void joint_block_kernel(const double* __restrict__ rec, const int* __
   o[18] = o[19] = 0.0;
 }
 
-// Σ over the workgroup of N per-lane values and the max of one more, in a fixed order (xor butterflies in each wave,
-// then the waves in order): out[0 … N) the sums, out[N] the max.  Every thread must call it.
-template <int N>
-__device__ __forceinline__ void wg_reduce_n(double (&v)[N], double m, double* out) {
-  __shared__ double s[N + 1][16];
-  for (int o = 32; o >= 1; o >>= 1) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) v[q] += __shfl_xor(v[q], o, 64);
-    m = fmax(m, __shfl_xor(m, o, 64));
-  }
-  const int w = threadIdx.x / 64, l = threadIdx.x % 64;
-  if (l == 0) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) s[q][w] = v[q];
-    s[N][w] = m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int nw = (int)(blockDim.x / 64);
-    for (int q = 0; q < N; ++q) {
-      double x = 0.0;
-      for (int i = 0; i < nw; ++i) x += s[q][i];
-      out[q] = x;
-    }
-    double x = 0.0;
-    for (int i = 0; i < nw; ++i) x = fmax(x, s[N][i]);
-    out[N] = x;
-  }
-}
-
 // One thread per point: its blocks' H_ρρ, g_ρ and W_h in block order; per workgroup max |g_ρ| over the points with
 // blocks (the LM loop's gradient norm).
 __global__ __launch_bounds__(256) void joint_point_kernel(const double* __restrict__ blk_data,
@@ -315,45 +285,8 @@ __global__ __launch_bounds__(256) void joint_point_kernel(const double* __restri
     if (q1 > q0) gm = fabs(g);
   }
   double none[1] = {0.0};
-  wg_reduce_n<1>(none, gm, gmax_p + 2 * blockIdx.x);
-}
-
-// T·exp(δ) (se3.hpp:763-784), the update of pba_gn.hip's se3_exp_mul
-__device__ void se3_plus(const double* T, const double* d, double* out) {
-  const double w0 = d[3], w1 = d[4], w2 = d[5];
-  const double th2 = w0 * w0 + w1 * w1 + w2 * w2, th = sqrt(th2);
-  double imag, real, A, B;
-  if (th < 1e-10) {
-    real = 1.0 - th2 / 8.0 + th2 * th2 / 384.0;
-    imag = 0.5 - th2 / 48.0 + th2 * th2 / 3840.0;
-    A = 0.5;
-    B = 1.0 / 6.0;
-  } else {
-    double sh, ch;
-    sincos(0.5 * th, &sh, &ch);
-    const double it = rcp_nr(th);
-    real = ch;
-    imag = sh * it;
-    A = 2.0 * imag * imag;
-    B = (th - 2.0 * sh * ch) * (it * it * it);
-  }
-  const double qx = imag * w0, qy = imag * w1, qz = imag * w2, qw = real;
-  const double v0 = d[0], v1 = d[1], v2 = d[2];
-  const double c0 = w1 * v2 - w2 * v1, c1 = w2 * v0 - w0 * v2, c2 = w0 * v1 - w1 * v0;
-  const double cc0 = w1 * c2 - w2 * c1, cc1 = w2 * c0 - w0 * c2, cc2 = w0 * c1 - w1 * c0;
-  const double tx = v0 + A * c0 + B * cc0, ty = v1 + A * c1 + B * cc1, tz = v2 + A * c2 + B * cc2;
-  const double ax = T[0], ay = T[1], az = T[2], aw = T[3];
-  const double rw = aw * qw - ax * qx - ay * qy - az * qz;
-  const double rx = aw * qx + ax * qw + ay * qz - az * qy;
-  const double ry = aw * qy + ay * qw + az * qx - ax * qz;
-  const double rz = aw * qz + az * qw + ax * qy - ay * qx;
-  const double n = rsqrt_nr(rw * rw + rx * rx + ry * ry + rz * rz);
-  double u0 = ay * tz - az * ty, u1 = az * tx - ax * tz, u2 = ax * ty - ay * tx;
-  u0 += u0; u1 += u1; u2 += u2;
-  out[0] = rx * n; out[1] = ry * n; out[2] = rz * n; out[3] = rw * n;
-  out[4] = T[4] + tx + aw * u0 + (ay * u2 - az * u1);
-  out[5] = T[5] + ty + aw * u1 + (az * u0 - ax * u2);
-  out[6] = T[6] + tz + aw * u2 + (ax * u1 - ay * u0);
+  double* const slot[1] = {gmax_p + 2 * blockIdx.x};
+  wg_reduce_sum_max<1>(none, gm, slot, slot[0] + 1);
 }
 
 // One thread per keyframe: the direct gradient and diagonal over its pairs (as host, then as target), its constants —
@@ -396,7 +329,7 @@ __global__ void joint_frame_kernel(const double* __restrict__ pair_rec, const in
     double ng[6], tg[7];
 #pragma unroll
     for (int r = 0; r < 6; ++r) ng[r] = -g[r];
-    se3_plus(poses + 7 * i, ng, tg);
+    se3_exp_mul(poses + 7 * i, ng, tg);
 #pragma unroll
     for (int r = 0; r < 7; ++r) gm = fmax(gm, fabs(poses[7 * i + r] - tg[r]));
   }
@@ -709,7 +642,7 @@ __global__ __launch_bounds__(256) void joint_update_kernel(const UpdArgs a) {
 #pragma unroll
       for (int r = 0; r < 7; ++r) T[r] = Tn[r] = a.poses[7 * i + r];
       if (!cp) {
-        se3_plus(T, d, Tn);
+        se3_exp_mul(T, d, Tn);
 #pragma unroll
         for (int r = 0; r < 7; ++r) {
           v[1] += (Tn[r] - T[r]) * (Tn[r] - T[r]);
@@ -729,12 +662,9 @@ __global__ __launch_bounds__(256) void joint_update_kernel(const UpdArgs a) {
       }
     }
   }
-  wg_reduce_n<3>(v, 0.0, a.red3 + 4 * blockIdx.x);
-}
-
-template <int PM>
-void launch_moments_pm(pba_engine* e, const KernelArgs& ka, double* rec, int grid) {
-  joint_moments_kernel<PM><<<grid, kBlockThreads, 0, e->stream>>>(ka, rec, (e->P + 7) / 8);
+  double* const r = a.red3 + 4 * blockIdx.x;
+  double* const slot[3] = {r, r + 1, r + 2};
+  wg_reduce_sum_max<3>(v, 0.0, slot, r + 3);
 }
 
 int ready(pba_engine* e) {
@@ -824,20 +754,6 @@ int ready(pba_engine* e) {
   return PBA_OK;
 }
 
-int sum_red(pba_engine* e, int slots, double* cost, double* n_valid) {
-  std::vector<double> h(2 * (size_t)slots);
-  PBA_HIP(hipMemcpyAsync(h.data(), e->joint.red.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
-  PBA_HIP(hipStreamSynchronize(e->stream));
-  double c = 0.0, v = 0.0;
-  for (int i = 0; i < slots; ++i) {
-    c += h[2 * i];
-    v += h[2 * i + 1];
-  }
-  *cost = c;
-  *n_valid = v;
-  return PBA_OK;
-}
-
 int linearize_j(pba_engine* e, double* cost) {
   JointSolve& J = e->joint;
   const int nf = e->n_frames;
@@ -852,16 +768,9 @@ int linearize_j(pba_engine* e, double* cost) {
   ka.poses = e->poses.p;  // the fused-state prologue, as the public evaluations
   ka.wg_red = J.red.p;
   const int grid = J.lin_slots;
-  switch (e->opt.camera_model + 4 * e->interp) {
-    case 0: launch_moments_pm<0>(e, ka, J.rec.p, grid); break;
-    case 1: launch_moments_pm<1>(e, ka, J.rec.p, grid); break;
-    case 2: launch_moments_pm<2>(e, ka, J.rec.p, grid); break;
-    case 3: launch_moments_pm<3>(e, ka, J.rec.p, grid); break;
-    case 4: launch_moments_pm<4>(e, ka, J.rec.p, grid); break;
-    case 5: launch_moments_pm<5>(e, ka, J.rec.p, grid); break;
-    case 6: launch_moments_pm<6>(e, ka, J.rec.p, grid); break;
-    default: launch_moments_pm<7>(e, ka, J.rec.p, grid); break;
-  }
+  dispatch_pm(e, [&](auto pm) {
+    joint_moments_kernel<decltype(pm)::value><<<grid, kBlockThreads, 0, e->stream>>>(ka, J.rec.p, (e->P + 7) / 8);
+  });
   PBA_HIP(hipGetLastError());
   if (e->n_pairs > 0)
     joint_pair_kernel<<<e->n_pairs, 64, 0, e->stream>>>(J.rec.p, J.pair_ptr.p, J.pair_blocks.p, e->pair_host.p,
@@ -878,7 +787,7 @@ int linearize_j(pba_engine* e, double* cost) {
   J.linearized = true;
   J.have_step = false;
   double c = 0.0;
-  if (int rc = sum_red(e, grid, &c, &J.n_valid)) return rc;
+  if (int rc = sum_red(e, J.red.p, grid, &c, &J.n_valid)) return rc;
   if (cost) *cost = c;
   return PBA_OK;
 }
@@ -938,7 +847,7 @@ int candidate_cost_j(pba_engine* e, double* cost, double* n_valid) {
   int slots = 0;
   if (int rc = launch_cost_only(e, e->pairs.p, J.rho_new.p, J.red.p, &slots, J.poses_new.p, nullptr, nullptr, J.ab_new.p))
     return rc;
-  return sum_red(e, slots, cost, n_valid);
+  return sum_red(e, J.red.p, slots, cost, n_valid);
 }
 
 int accept_j(pba_engine* e) {
@@ -991,16 +900,8 @@ int pba_joint_get_reduced_system(pba_engine* e, double* S_dense, double* g) {
     std::vector<double> S((size_t)64 * J.n_sky);
     PBA_HIP(hipMemcpyAsync(S.data(), J.S.p, sizeof(double) * S.size(), hipMemcpyDeviceToHost, e->stream));
     PBA_HIP(hipStreamSynchronize(e->stream));
-    std::fill(S_dense, S_dense + n * n, 0.0);
-    for (int i = 0; i < nf; ++i)
-      for (int j = J.first_h[i]; j <= i; ++j) {
-        const double* B = &S[64 * (size_t)(J.row_h[i] + (j - J.first_h[i]))];
-        for (int r = 0; r < 8; ++r)
-          for (int c = 0; c < (i == j ? r + 1 : 8); ++c) {  // (a diagonal block's lower triangle is what is factored)
-            S_dense[(8 * i + r) * n + 8 * j + c] = B[8 * r + c];
-            S_dense[(8 * j + c) * n + 8 * i + r] = B[8 * r + c];
-          }
-      }
+    // (a diagonal block's lower triangle is what is factored)
+    skyline_to_dense<8>(S, J.first_h, J.row_h, nf, true, [](int, int, int, int, double v) { return v; }, S_dense);
   }
   if (g) {
     PBA_HIP(hipMemcpyAsync(g, J.g.p, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
@@ -1035,102 +936,28 @@ int pba_joint_accept(pba_engine* e) {
   return accept_j(e);
 }
 
-// Ceres' trust-region loop with the LM strategy (trust_region_minimizer.cc:67-136, levenberg_marquardt_strategy.cc), host
-// driven, in the order of tests tests/gn_reference.py::lm restates; norms over the free poses (ambient [q | t]), the ρ
-// of points with blocks and the free (a, b).
+// The host-driven trust-region loop (pba_host_lm.h); norms over the free poses (ambient [q | t]), the ρ of points with
+// blocks and the free (a, b).  ‖x‖ after an accepted step is its candidate's, from the step's ‖candidate‖².
 int pba_solve_joint(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum) {
   if (int rc = ready(e)) return rc;
-  pba_solver_options opt{20, 5, 1e4, 1e-6, 1e-8, 1e-3, 1e-10, 1e16, 1e-32};
-  if (o) opt = *o;
-  if (opt.max_num_consecutive_invalid_steps <= 0) opt.max_num_consecutive_invalid_steps = 5;
-  const auto t0 = std::chrono::steady_clock::now();
-  JointSolve& J = e->joint;
-  pba_solver_summary s{};
-  s.termination = PBA_TERMINATION_MAX_ITERATIONS;
-  s.stop_reason = PBA_STOP_MAX_ITERATIONS;
-  std::vector<pba_iteration_summary>& hist = e->gn.history;
-  hist.clear();
-  double cost = 0.0, gmax = 0.0;
-  if (int rc = linearize_j(e, &cost)) return rc;
-  if (int rc = gradient_norm(e, &gmax)) return rc;
-  s.initial_cost = cost;
-  double radius = opt.initial_trust_region_radius, factor = 2.0, x_norm = -1.0;
-  int invalid = 0, it = 0;
-  hist.push_back({0, 1, 1, 0, cost, 0.0, 0.0, radius, 0.0, gmax});
-  auto finish = [&](int term, int reason) {
-    s.termination = term;
-    s.stop_reason = reason;
-  };
-  if (gmax <= opt.gradient_tolerance) {
-    finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_GRADIENT_TOLERANCE);
-  } else {
-    for (it = 1; it <= opt.max_iterations; ++it) {
-      double model = 0.0, ss = 0.0, xx = 0.0, cand = 0.0, nv = 0.0;
-      int st = 0;
-      if (int rc = step_j(e, 1.0 / radius, &model, &st, &ss, &xx)) return rc;
-      if (st != 0 || !(model > 0.0)) {  // invalid step
-        if (++invalid >= opt.max_num_consecutive_invalid_steps) {
-          finish(PBA_TERMINATION_FAILURE, PBA_STOP_INVALID_STEPS);
-          --it;
-          break;
-        }
-        radius /= factor;
-        factor *= 2.0;
-        ++s.unsuccessful_steps;
-        hist.push_back({it, 0, 0, 0, cost, 0.0, 0.0, radius, 0.0, gmax});
-        if (radius <= opt.min_trust_region_radius) {
-          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_MIN_TRUST_REGION_RADIUS);
-          break;
-        }
-        continue;
-      }
-      invalid = 0;
-      const double n_valid = J.n_valid;
-      if (int rc = candidate_cost_j(e, &cand, &nv)) return rc;
-      if (nv < n_valid) cand = DBL_MAX;  // a failed evaluation (pba_solve's rule)
-      const double step = std::sqrt(ss);
-      if (step <= opt.parameter_tolerance * (x_norm + opt.parameter_tolerance)) {
-        finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_PARAMETER_TOLERANCE);
-        break;
-      }
-      if (std::fabs(cost - cand) <= opt.function_tolerance * cost) {
-        finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_FUNCTION_TOLERANCE);
-        break;
-      }
-      const double rel = (cost - cand) / model;
-      if (rel > opt.min_relative_decrease) {
-        if (int rc = accept_j(e)) return rc;
-        const double before = cost;
-        if (int rc = linearize_j(e, &cost)) return rc;  // (its cost is the candidate's: the same rows at the same state)
-        if (int rc = gradient_norm(e, &gmax)) return rc;
-        x_norm = std::sqrt(xx);
-        radius = std::min(opt.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3)));
-        factor = 2.0;
-        ++s.successful_steps;
-        hist.push_back({it, 1, 1, 0, cost, before - cost, rel, radius, step, gmax});
-        if (it < opt.max_iterations && gmax <= opt.gradient_tolerance) {
-          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_GRADIENT_TOLERANCE);
-          break;
-        }
-      } else {
-        radius /= factor;
-        factor *= 2.0;
-        ++s.unsuccessful_steps;
-        hist.push_back({it, 0, 1, 0, cand, cost - cand, rel, radius, step, gmax});
-        if (radius <= opt.min_trust_region_radius) {
-          finish(PBA_TERMINATION_CONVERGENCE, PBA_STOP_MIN_TRUST_REGION_RADIUS);
-          break;
-        }
-      }
-    }
-    if (it > opt.max_iterations) it = opt.max_iterations;
-  }
-  s.iterations = it;
-  s.final_cost = cost;
-  s.gradient_max_norm = gmax;
-  s.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (sum) *sum = s;
-  return PBA_OK;
+  double sq_x = 0.0;
+  HostLmStages stages{
+      [&](double* cost, double* gmax, double* x_norm) {
+        if (int rc = linearize_j(e, cost)) return rc;
+        *x_norm = std::sqrt(sq_x);
+        return gradient_norm(e, gmax);
+      },
+      [&](double lambda, int* status, double* model, double* sq_step) {
+        return step_j(e, lambda, model, status, sq_step, &sq_x);
+      },
+      [&](double* cost) {
+        double nv = 0.0;
+        if (int rc = candidate_cost_j(e, cost, &nv)) return rc;
+        if (nv < e->joint.n_valid) *cost = DBL_MAX;  // a failed evaluation (pba_solve's rule)
+        return PBA_OK;
+      },
+      [&]() { return accept_j(e); }};
+  return host_lm(o, stages, e->gn.history, sum);
 }
 
 }  // extern "C"

@@ -4,18 +4,10 @@
 #include <algorithm>
 
 #include "pba_gn_plan.h"
+#include "pba_plan_lists.h"
 
 namespace pba {
 namespace detail {
-
-namespace {
-
-// CSR from a count-then-fill pass: ptr from the counts in ptr[1…], then `at` as the running cursors
-void prefix(std::vector<int>& ptr) {
-  for (size_t i = 0; i + 1 < ptr.size(); ++i) ptr[i + 1] += ptr[i];
-}
-
-}  // namespace
 
 bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
   const int nf = in.n_frames, np = in.n_pairs, npt = in.n_points, nb = in.n_blocks;
@@ -30,37 +22,9 @@ bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
     if (in.block_pair[b] < 0 || in.block_pair[b] >= np || in.block_point[b] < 0 || in.block_point[b] >= npt) return false;
     if (in.pair_host[in.block_pair[b]] != in.point_host[in.block_point[b]]) return false;
   }
-  // blocks of each pair and of each point (counting sorts: ascending)
-  P.pair_ptr.assign(np + 1, 0);
-  P.pt_ptr.assign(npt + 1, 0);
-  for (int b = 0; b < nb; ++b) {
-    ++P.pair_ptr[in.block_pair[b] + 1];
-    ++P.pt_ptr[in.block_point[b] + 1];
-  }
-  prefix(P.pair_ptr);
-  prefix(P.pt_ptr);
-  P.pair_blocks.resize(nb);
-  P.pt_blocks.resize(nb);
-  {
-    std::vector<int> at(P.pair_ptr.begin(), P.pair_ptr.end() - 1), aq(P.pt_ptr.begin(), P.pt_ptr.end() - 1);
-    for (int b = 0; b < nb; ++b) {
-      P.pair_blocks[at[in.block_pair[b]]++] = b;
-      P.pt_blocks[aq[in.block_point[b]]++] = b;
-    }
-  }
-  // pairs of each keyframe: as host, then as target
-  P.frame_ptr.assign(nf + 1, 0);
-  for (int p = 0; p < np; ++p) {
-    ++P.frame_ptr[in.pair_host[p] + 1];
-    ++P.frame_ptr[in.pair_target[p] + 1];
-  }
-  prefix(P.frame_ptr);
-  P.frame_pairs.resize(2 * (size_t)np);
-  {
-    std::vector<int> at(P.frame_ptr.begin(), P.frame_ptr.end() - 1);
-    for (int p = 0; p < np; ++p) P.frame_pairs[at[in.pair_host[p]]++] = 2 * p;
-    for (int p = 0; p < np; ++p) P.frame_pairs[at[in.pair_target[p]]++] = 2 * p + 1;
-  }
+  csr_group(np, nb, in.block_pair, P.pair_ptr, P.pair_blocks);
+  csr_group(npt, nb, in.block_point, P.pt_ptr, P.pt_blocks);
+  frame_pair_lists(nf, np, in.pair_host, in.pair_target, P.frame_ptr, P.frame_pairs);
   auto target_of = [&](int b) { return in.pair_target[in.block_pair[b]]; };
   // skyline profile: every two keyframes of one point share a block of the reduced system
   P.first.resize(nf);
@@ -78,22 +42,9 @@ bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
   skyline_profile(P.first, P.row, P.last, P.colptr, P.colrows);
   P.n_sky = P.row[nf];
   auto sky = [&](int i, int j) { return P.row[i] + (j - P.first[i]); };  // i ≥ j ≥ first[i]
-  // pairs of each off-diagonal skyline block
-  P.off_ptr.assign(P.n_sky + 1, 0);
-  auto sky_pair = [&](int p) {
-    const int h = in.pair_host[p], t = in.pair_target[p];
-    return sky(std::max(h, t), std::min(h, t));
-  };
-  for (int p = 0; p < np; ++p)
-    if (P.pair_ptr[p] < P.pair_ptr[p + 1]) ++P.off_ptr[sky_pair(p) + 1];  // (a pair without blocks lies in no point's span)
-  prefix(P.off_ptr);
-  P.off_pairs.resize(P.off_ptr[P.n_sky]);
-  {
-    std::vector<int> at(P.off_ptr.begin(), P.off_ptr.end() - 1);
-    for (int p = 0; p < np; ++p)
-      if (P.pair_ptr[p] < P.pair_ptr[p + 1])
-        P.off_pairs[at[sky_pair(p)]++] = 2 * p + (in.pair_host[p] < in.pair_target[p] ? 1 : 0);
-  }
+  // (self pairs are refused above; a pair without blocks lies in no point's span, so it takes no part)
+  off_diagonal_pair_lists(np, in.pair_host, in.pair_target, P.first, P.row,
+                          [&](int p) { return P.pair_ptr[p] < P.pair_ptr[p + 1]; }, P.off_ptr, P.off_pairs);
   // Schur terms per skyline block and entries per keyframe: two passes over the points' entries (count, fill)
   auto frame_of = [&](int e) { return e < 0 ? in.point_host[~e] : target_of(e); };
   P.term_ptr.assign(P.n_sky + 1, 0);
@@ -120,8 +71,8 @@ bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
       }
     }
     if (pass == 0) {
-      prefix(P.term_ptr);
-      prefix(P.fe_ptr);
+      csr_prefix(P.term_ptr);
+      csr_prefix(P.fe_ptr);
       P.terms.resize(P.term_ptr[P.n_sky]);
       P.fe_entries.resize(P.fe_ptr[nf]);
       at_t.assign(P.term_ptr.begin(), P.term_ptr.end() - 1);

@@ -381,6 +381,23 @@ def test_solve_affine_brings_brightness_back():
     assert np.abs(ab - ab_ref).max() <= 1e-3 and not ab[0].any()
 
 
+# the trial that meets the function tolerance is not applied: one iteration, the state bit for bit the initial one
+def test_solve_affine_function_tolerance_applies_nothing():
+    pb = R.problem()
+    with open_engine(pb, None, switch=False) as eng:
+        eng.set_fixed_affine_frames(np.array([0], np.int32))
+        before = (*eng.get_state(), eng.get_affine_state())
+        summ = eng.solve_affine(function_tolerance=1.0)
+        its = eng.solver_iterations()
+        after = (*eng.get_state(), eng.get_affine_state())
+    print(f"\nsolve_affine(function_tolerance=1): {summ}")
+    assert summ["iterations"] == 1 and summ["stop_reason"] == "function_tolerance" and summ["termination"] == 0
+    assert summ["successful_steps"] == 0 and summ["unsuccessful_steps"] == 0 and len(its["cost"]) == 1
+    assert summ["final_cost"] == summ["initial_cost"] > 0
+    for a, b in zip(before, after):
+        assert np.array_equal(a, b)
+
+
 # 6. in turn: three rounds of solve, then solve_affine
 def test_alternation():
     pb = R.problem()

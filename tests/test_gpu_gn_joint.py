@@ -251,6 +251,22 @@ def test_solve_joint_rejects_a_trial():
     same_lm(summ, its, ref)
 
 
+# the trial that meets the function tolerance is not applied: one iteration, the state bit for bit the initial one
+def test_solve_joint_function_tolerance_applies_nothing():
+    pb = R.problem()
+    with open_engine(pb, None) as eng:
+        before = (*eng.get_state(), eng.get_affine_state())
+        summ = eng.solve_joint(function_tolerance=1.0)
+        its = eng.solver_iterations()
+        after = (*eng.get_state(), eng.get_affine_state())
+    print(f"\nsolve_joint(function_tolerance=1): {summ}")
+    assert summ["iterations"] == 1 and summ["stop_reason"] == "function_tolerance" and summ["termination"] == 0
+    assert summ["successful_steps"] == 0 and summ["unsuccessful_steps"] == 0 and len(its["cost"]) == 1
+    assert summ["final_cost"] == summ["initial_cost"] > 0
+    for a, b in zip(before, after):
+        assert np.array_equal(a, b)
+
+
 # 6. reproducible: two engines, two runs each — the system, the step and the solve bitwise equal
 def test_reproducible():
     pb = R.problem(P=12, cams=2)
