@@ -283,7 +283,8 @@ int pba_affine_accept(pba_engine* engine);
  * constants as identity / 0, and g_S — testing and inspection.  pba_joint_get_step: δ of the keyframes (8·n_frames) and
  * δρ (n_points); either may be NULL.  pba_joint_accept: poses, ρ and affine state ← candidate.
  * Every sum is fp64 in a fixed order, so results are bitwise reproducible.  They work at the engine's current pyramid
- * level; (a, b) carry no level factor.  Single GPU.
+ * level; (a, b) carry no level factor.  One GPU; over several: pba_joint_step_export / import and
+ * pba_solve_joint_distributed, below the multi-GPU Gauss-Newton.
  * pba_solve_joint: Ceres' trust-region loop (trust_region_minimizer.cc:67-136) driven from the host as pba_solve_affine
  * is, norms over the free poses (ambient [q | t]), the ρ of points with blocks and the free (a, b); a candidate with
  * fewer valid blocks than the current state counts as a failed evaluation (pba_solve's rule); fills the summary (the
@@ -518,6 +519,55 @@ int pba_comm_allreduce(pba_comm* comm, double* d_buf, int64_t count, void* hip_s
 /* pba_solve_distributed over a communicator, with an exchange buffer owned by the engine */
 int pba_solve_distributed_comm(pba_engine* engine, const pba_solver_options* options, int32_t band, pba_comm* comm,
                                pba_solver_summary* summary);
+
+/* Multi-GPU joint solve of poses, inverse distances and (a, b) -------------------------------------------
+ * The arrangement above for the joint solve (pba_joint_linearize): every engine holds ALL keyframes (global indices,
+ * identical poses and identical affine state) and the points hosted by its shard of keyframes with all their blocks, so
+ * the inverse distances are eliminated locally.  Rank r contributes its undamped keyframe system with its points
+ * eliminated at λ, S_r = A_r − B_r (C_r + λ·clamp(C_r))⁻¹ B_rᵀ, its Schur gradient, its direct gradient, its undamped
+ * direct diagonal and, per keyframe, the number of valid blocks on it.  Damping and constants come AFTER the sum,
+ * because a rank cannot decide them (a keyframe without a valid block on this rank may have one on another): every rank
+ * adds λ·clamp(diag, 1e-6, 1e32) on the free diagonal, makes a keyframe's pose constant when it is in
+ * pba_set_fixed_frames or its summed count is 0, its (a, b) constant when it is in pba_set_fixed_affine_frames, its
+ * summed count is 0 or its a or b is not finite, solves the same system, back-substitutes its own δρ and forms its
+ * candidate.
+ *
+ * The exchange buffer is a DEVICE array of pba_joint_exchange_size doubles, banded with K block rows, any K with
+ * max over ranks of pba_joint_band ≤ K ≤ n_frames − 1 (the summed system is solved as a skyline over the band's
+ * profile): per keyframe i, (K+1) row-major 8×8 blocks (block c = column i−K+c; blocks left of column 0 and blocks
+ * outside the rank's own profile are zeros), followed by 32 doubles [g_S(8) | g_direct(8) | diag(8) | valid blocks on
+ * the keyframe | 0…]; after all keyframes, 16 scalar slots.  An export writes every double of the buffer (the scalar
+ * slots as zeros), in fp64 sums of a fixed order: two exports of one linearisation are bit-identical, and two ranks
+ * importing the same buffer get the same keyframe step bit for bit.
+ *
+ * pba_joint_step_export: after pba_joint_linearize, the point elimination for lambda and this rank's contribution.
+ * pba_joint_step_import: d_exchange holds the sum over the ranks of exports at the same lambda and band — damping,
+ * constants, solve, this rank's δρ and candidate.  model_keyframes is the keyframes' part of the model decrease
+ * (identical on every rank, to be counted once), model_points this rank's points'.  After an import
+ * pba_joint_get_reduced_system and pba_joint_get_step serve the summed damped system and the step, and
+ * pba_joint_candidate_cost (this rank's blocks) and pba_joint_accept work as after pba_joint_step.
+ * pba_solve_joint_distributed: pba_solve_joint over all ranks with the host-callback collective of
+ * pba_solve_distributed (the joint loop is host-driven; there is no pba_comm variant).  Per linearisation the scalar
+ * slots are summed once (cost, valid blocks, ‖x‖² of this rank's points, this rank's groups of 256 points with a
+ * gradient entry above the tolerance); per trial the system (pba_joint_exchange_size − 16 doubles), then the scalar
+ * slots (the points' part of the model decrease, the candidate's cost and valid blocks, ‖δ‖² and ‖x‖² of this rank's
+ * points).  The keyframes' parts are computed by every rank from the same summed buffer and counted once, so every
+ * rank decides from bit-identical numbers and no decision is exchanged.  Summary, trajectory, the rule for a candidate
+ * with fewer valid blocks (over all ranks) and staleness as pba_solve_joint.  gradient_max_norm is rank-local:
+ * max(the keyframes' part, this rank's points), the keyframes' part being that of the last summed system (a
+ * linearisation's own only after its first trial); the gradient-tolerance stop uses the summed count, and where that
+ * is 0 one more sum of the system (exported at λ = 0) gives the linearisation's own keyframe part.
+ * PBA_ERR_INVALID_ARGUMENT: an engine pba_joint_linearize refuses, a band below pba_joint_band or above n_frames − 1,
+ * a null buffer or callback.  PBA_ERR_NOT_READY: an export before pba_joint_linearize, an import before an export of
+ * this linearisation at the same lambda and band, and an engine without blocks — the caller chooses keyframe ranges
+ * that leave at least one block on every rank. */
+int pba_joint_band(pba_engine* engine, int32_t* band);   /* local bandwidth of the 8×8-block system, block rows */
+int pba_joint_exchange_size(pba_engine* engine, int32_t band, int64_t* count);   /* doubles */
+int pba_joint_step_export(pba_engine* engine, double lambda, int32_t band, double* d_exchange);
+int pba_joint_step_import(pba_engine* engine, double lambda, int32_t band, const double* d_exchange,
+                          double* model_keyframes, double* model_points, int32_t* solver_status);
+int pba_solve_joint_distributed(pba_engine* engine, const pba_solver_options* options, int32_t band, double* d_exchange,
+                                pba_allreduce_fn allreduce, void* user, pba_solver_summary* summary);
 
 /* Image pyramid / coarse-to-fine ------------------------------------------
  * pba_build_pyramid builds levels 1 … n−1 on the device from the current frames, cameras and points (DSO

@@ -1013,6 +1013,19 @@ struct JointSolve {
   pba::detail::DevBuf<double> poses_new, rho_new, ab_new;
   pba::detail::DevBuf<double> red, red3;
   pba::detail::DevBuf<int> status;
+  // The multi-GPU exchange (pba_joint_step_export / import): the plan of the last band K (−1: none) and the summed
+  // system's storage over the band profile.  lin_id counts the linearisations; an export stands for the linearisation,
+  // λ and band it was made at.  step_band: the last step came from an import (the getters then serve the band storage).
+  int ex_K = -1, ex_n_sky = 0;
+  long long ex_stride = 0, ex_scalar_off = 0, ex_count = 0;
+  long long lin_id = 0, ex_lin = -1;
+  double ex_lambda = 0.0;
+  int ex_band = -1;
+  bool step_band = false;
+  std::vector<int> ex_first_h, ex_row_h;
+  pba::detail::DevBuf<int> ex_src, ex_first, ex_row, ex_colptr, ex_colrows, ex_sky_i, ex_sky_j;
+  pba::detail::DevBuf<uint8_t> ex_cst;                 // the constants decided after the sum
+  pba::detail::DevBuf<double> ex_S, ex_L, ex_frame, ex_gmax_f, red6;  // ex_frame: the summed direct gradient and diagonal
 };
 
 struct pba_engine {

@@ -667,6 +667,204 @@ __global__ __launch_bounds__(256) void joint_update_kernel(const UpdArgs a) {
   wg_reduce_sum_max<3>(v, 0.0, slot, r + 3);
 }
 
+// ---- the multi-GPU exchange (pba.h pba_joint_step_export / import; the layout: pba_joint_plan.h) ---------------------
+struct ExArgsJ {
+  AsmArgsJ a;      // the sources; its cst, S, L, g and lambda are not read
+  const int* src;  // per (keyframe, band column): the local skyline block, −1 none
+  double* X;
+  int K;
+  long long stride;
+};
+
+// This rank's undamped reduced system into the exchange buffer.  Workgroups [0, n_frames·(K + 1)): one per (keyframe,
+// band column) block, thread = element — joint_assemble_kernel's sums in its order (the direct pair terms, then the Schur
+// terms), without its damping and constants, which are decided after the sum over the ranks; zeros where the rank has
+// no block.  The next n_frames workgroups: the keyframe's tail — joint_gradient_kernel's sum without its constant mask,
+// the direct gradient and diagonal of frame_data, and the valid blocks of the keyframe's pairs in list order.  The last
+// workgroup clears the scalar slots, so every double of the buffer is written.
+__global__ __launch_bounds__(64) void joint_export_kernel(const ExArgsJ x) {
+  const AsmArgsJ& a = x.a;
+  const int w = blockIdx.x, t = threadIdx.x, nb = a.n_frames * (x.K + 1);
+  if (w < nb) {
+    const int i = w / (x.K + 1), cb = w % (x.K + 1), s = x.src[w], r = t >> 3, c = t & 7;
+    double v = 0.0;
+    if (s >= 0) {
+      if (cb == x.K) {
+        for (int q = a.frame_ptr[i]; q < a.frame_ptr[i + 1]; ++q) {
+          const int e = a.frame_pairs[q], o = (e & 1) ? 8 : 0;
+          v += a.pair_rec[(long long)(e >> 1) * kPairRec + (o + r) * 16 + o + c];
+        }
+      } else {
+        for (int q = a.off_ptr[s]; q < a.off_ptr[s + 1]; ++q) {
+          const int e = a.off_pairs[q];
+          const double* pr = a.pair_rec + (long long)(e >> 1) * kPairRec;
+          v += (e & 1) ? pr[(8 + r) * 16 + c] : pr[r * 16 + 8 + c];
+        }
+      }
+      for (int q = a.term_ptr[s]; q < a.term_ptr[s + 1]; ++q) {
+        const int2 tm = a.terms[q];
+        int p, p2;
+        const double* wa = entry_w(a, tm.x, &p);
+        const double* wb = entry_w(a, tm.y, &p2);
+        v -= wa[r] * wb[c] * a.inv[p];
+      }
+    }
+    x.X[(long long)i * x.stride + cb * 64 + t] = v;
+  } else if (w < nb + a.n_frames) {
+    if (t >= kJointExTail) return;
+    const int i = w - nb;
+    double v = 0.0;
+    if (t < 8) {
+      v = a.frame_data[(long long)i * kFrame + t];
+      for (int q = a.fe_ptr[i]; q < a.fe_ptr[i + 1]; ++q) {
+        int p;
+        const double* wv = entry_w(a, a.fe_entries[q], &p);
+        v -= wv[t] * a.pt_data[(long long)p * kPt + 1] * a.inv[p];
+      }
+    } else if (t < 24) {
+      v = a.frame_data[(long long)i * kFrame + t - 8];
+    } else if (t == 24) {
+      for (int q = a.frame_ptr[i]; q < a.frame_ptr[i + 1]; ++q)
+        v += a.pair_rec[(long long)(a.frame_pairs[q] >> 1) * kPairRec + 272];
+    }
+    x.X[(long long)i * x.stride + (long long)(x.K + 1) * 64 + t] = v;
+  } else if (t < kJointExScalars) {
+    x.X[(long long)a.n_frames * x.stride + t] = 0.0;
+  }
+}
+
+struct ImpArgsJ {
+  const double* X;  // the sum over the ranks
+  const uint8_t* fixed;
+  const double *poses, *ab;
+  const int *sky_i, *sky_j;
+  double *S, *L, *g, *frame_data, *gmax_f;
+  uint8_t* cst;
+  int K;
+  long long stride;
+  double lambda;
+};
+
+// joint_frame_kernel's constants from the summed count of valid blocks: half 0 the pose, 1 the (a, b)
+__device__ __forceinline__ bool import_constant(const ImpArgsJ& a, int i, int half) {
+  const bool seen = a.X[(long long)i * a.stride + (long long)(a.K + 1) * 64 + 24] > 0.0;
+  if (half == 0) return a.fixed[2 * i] != 0 || !seen;
+  return a.fixed[2 * i + 1] != 0 || !seen || !isfinite(a.ab[2 * i]) || !isfinite(a.ab[2 * i + 1]);
+}
+
+// The summed band into factor storage over the band profile: one 64-thread workgroup per block (i, j), thread =
+// element, with joint_assemble_kernel's damping and constants from the summed diagonal and the summed counts.  The
+// diagonal workgroups also write their keyframe's g_S (0 for a constant), the summed direct gradient and diagonal in
+// frame_data's layout, the constant mask the update reads, and joint_frame_kernel's gradient norm from the summed
+// direct gradient.  Every rank runs this on the same buffer: the same system bit for bit.
+__global__ __launch_bounds__(64) void joint_import_kernel(const ImpArgsJ a) {
+  const int s = blockIdx.x, t = threadIdx.x, r = t >> 3, c = t & 7;
+  const int i = a.sky_i[s], j = a.sky_j[s];
+  const double* tail = a.X + (long long)i * a.stride + (long long)(a.K + 1) * 64;
+  double v = a.X[(long long)i * a.stride + (long long)(j - (i - a.K)) * 64 + t];
+  const bool ci = import_constant(a, i, r >= 6), cj = import_constant(a, j, c >= 6);
+  if (ci || cj) v = i == j && r == c ? 1.0 : 0.0;
+  else if (i == j && r == c) v += a.lambda * lm_clamp(tail[16 + r]);
+  a.S[(long long)s * 64 + t] = v;
+  a.L[(long long)s * 64 + t] = v;
+  if (i != j) return;
+  if (t < 8) {
+    a.g[8 * i + t] = import_constant(a, i, t >= 6) ? 0.0 : tail[t];
+  } else if (t < 24) {
+    a.frame_data[(long long)i * kFrame + t - 8] = tail[t];
+  } else if (t < 26) {
+    a.cst[2 * i + t - 24] = import_constant(a, i, t - 24) ? 1 : 0;
+  } else if (t == 26) {
+    double gm = 0.0;
+    if (!import_constant(a, i, 0)) {
+      double ng[6], tg[7];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) ng[q] = -tail[8 + q];
+      se3_exp_mul(a.poses + 7 * i, ng, tg);
+#pragma unroll
+      for (int q = 0; q < 7; ++q) gm = fmax(gm, fabs(a.poses[7 * i + q] - tg[q]));
+    }
+    if (!import_constant(a, i, 1)) gm = fmax(gm, fmax(fabs(tail[14]), fabs(tail[15])));
+    a.gmax_f[i] = gm;
+  }
+}
+
+// joint_update_kernel for a step from the summed system, with the keyframe and the point parts of its three sums in
+// separate slots (0…2 the points', 3…5 the keyframes'): the point parts differ from rank to rank and are summed over the
+// ranks, the keyframe parts are every rank's own copy of one number.  The keyframes come first, threads [0, n_frames),
+// so that their partition into workgroups, and with it the order of their sums, is the same on every rank; the points
+// follow, threads [n_frames, n_frames + n_points).
+__global__ __launch_bounds__(256) void joint_update_parts_kernel(const UpdArgs a) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (*a.status == 0) {
+    if (u < a.n_frames) {
+      const int i = u;
+      const double* fd = a.frame_data + (long long)i * kFrame;
+      const bool cp = a.cst[2 * i] != 0, ca = a.cst[2 * i + 1] != 0;
+      double d[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        d[r] = (r < 6 ? cp : ca) ? 0.0 : a.x[8 * i + r];
+        if (!(r < 6 ? cp : ca)) v[3] += a.lambda * lm_clamp(fd[8 + r]) * d[r] * d[r] - fd[r] * d[r];
+      }
+      double T[7], Tn[7];
+#pragma unroll
+      for (int r = 0; r < 7; ++r) T[r] = Tn[r] = a.poses[7 * i + r];
+      if (!cp) {
+        se3_exp_mul(T, d, Tn);
+#pragma unroll
+        for (int r = 0; r < 7; ++r) {
+          v[4] += (Tn[r] - T[r]) * (Tn[r] - T[r]);
+          v[5] += Tn[r] * Tn[r];
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 7; ++r) a.poses_new[7 * i + r] = Tn[r];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const double o = a.ab[2 * i + r], n = ca ? o : o + d[6 + r];
+        a.ab_new[2 * i + r] = n;
+        if (!ca) {
+          v[4] += d[6 + r] * d[6 + r];
+          v[5] += n * n;
+        }
+      }
+    } else if (u < a.n_frames + a.n_points) {
+      const int p = u - a.n_frames;
+      const double* pd = a.pt_data + (long long)p * kPt;
+      const double inv = a.inv[p];
+      const int q0 = a.pt_ptr[p], q1 = a.pt_ptr[p + 1];
+      double d = 0.0;
+      if (inv > 0.0) {
+        double acc = pd[1];
+        const double* xh = a.x + 8 * a.point_host[p];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) acc += pd[4 + r] * xh[r];
+        for (int q = q0; q < q1; ++q) {
+          const int b = a.pt_blocks[q];
+          const double* w = a.blk_data + (long long)b * kBlk + 2;
+          const double* xt = a.x + 8 * a.block_rec[b].z;
+#pragma unroll
+          for (int r = 0; r < 8; ++r) acc += w[r] * xt[r];
+        }
+        d = -acc * inv;
+        v[0] = a.lambda * lm_clamp(pd[0]) * d * d - pd[1] * d;
+      }
+      const double rn = a.rho[p] + d;
+      a.drho[p] = d;
+      a.rho_new[p] = rn;
+      if (q1 > q0) {
+        v[1] = d * d;
+        v[2] = rn * rn;
+      }
+    }
+  }
+  double* const r = a.red3 + 8 * blockIdx.x;
+  double* const slot[6] = {r, r + 1, r + 2, r + 3, r + 4, r + 5};
+  wg_reduce_sum_max<6>(v, 0.0, slot, r + 6);
+}
+
 int ready(pba_engine* e) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
   if (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC || !e->affine)
@@ -750,6 +948,7 @@ int ready(pba_engine* e) {
     PBA_HIP(J.status.resize(1));
     J.planned = true;
     J.linearized = J.have_step = false;
+    J.ex_K = -1;  // (the exchange plan is the profile's)
   }
   return PBA_OK;
 }
@@ -786,6 +985,7 @@ int linearize_j(pba_engine* e, double* cost) {
   PBA_HIP(hipGetLastError());
   J.linearized = true;
   J.have_step = false;
+  ++J.lin_id;  // (an export stands for one linearisation)
   double c = 0.0;
   if (int rc = sum_red(e, J.red.p, grid, &c, &J.n_valid)) return rc;
   if (cost) *cost = c;
@@ -835,6 +1035,7 @@ int step_j(pba_engine* e, double lambda, double* model, int* status, double* sq_
     xx += h[4 * s + 2];
   }
   J.have_step = st == 0;
+  J.step_band = false;
   if (status) *status = st != 0 ? 1 : 0;
   if (model) *model = st == 0 ? 0.5 * m : 0.0;
   if (sq_step) *sq_step = ss;
@@ -861,6 +1062,125 @@ int accept_j(pba_engine* e) {
   e->pairs_fresh = false;
   e->evaluated = false;
   e->res_fresh = false;
+  return PBA_OK;
+}
+
+// ---- the multi-GPU exchange: host side -------------------------------------------------------------------------------
+int local_band(const pba_engine* e) { return joint_local_band(e->joint.first_h); }
+
+int check_band(pba_engine* e, int band) {
+  if (band < local_band(e) || band > e->n_frames - 1)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "band must lie between pba_joint_band (" + std::to_string(local_band(e)) +
+                                              ") and n_frames - 1 (" + std::to_string(e->n_frames - 1) + ")");
+  return PBA_OK;
+}
+
+// the exchange plan and the band storage for K (kept until K or the problem changes)
+int ensure_exchange(pba_engine* e, int K) {
+  JointSolve& J = e->joint;
+  if (J.ex_K == K) return PBA_OK;
+  JointExchangePlan X;
+  if (!build_joint_exchange(J.first_h, J.row_h, K, X)) return fail(PBA_ERR_INVALID_ARGUMENT, "band out of range");
+  const size_t nf = e->n_frames;
+  J.ex_K = -1;
+  PBA_HIP(J.ex_src.upload(X.src, e->stream));
+  PBA_HIP(J.ex_first.upload(X.first, e->stream));
+  PBA_HIP(J.ex_row.upload(X.row, e->stream));
+  PBA_HIP(J.ex_colptr.upload(X.colptr, e->stream));
+  PBA_HIP(J.ex_colrows.upload(X.colrows, e->stream));
+  PBA_HIP(J.ex_sky_i.upload(X.sky_i, e->stream));
+  PBA_HIP(J.ex_sky_j.upload(X.sky_j, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));  // (the plan's vectors die with this scope)
+  PBA_HIP(J.ex_S.resize(64 * (size_t)X.n_sky));
+  PBA_HIP(J.ex_L.resize(64 * (size_t)X.n_sky));
+  PBA_HIP(J.ex_cst.resize(2 * nf));
+  PBA_HIP(J.ex_frame.resize(nf * kFrame));
+  PBA_HIP(J.ex_gmax_f.resize(nf));
+  PBA_HIP(J.red6.resize(8 * (size_t)J.upd_slots));
+  J.ex_first_h = X.first;
+  J.ex_row_h = X.row;
+  J.ex_n_sky = X.n_sky;
+  J.ex_stride = X.stride;
+  J.ex_scalar_off = X.scalar_off;
+  J.ex_count = X.count;
+  J.ex_K = K;
+  J.ex_lin = -1;
+  return PBA_OK;
+}
+
+int export_j(pba_engine* e, double lambda, int K, double* X) {
+  JointSolve& J = e->joint;
+  if (int rc = ensure_exchange(e, K)) return rc;
+  const int nf = e->n_frames, npt = e->n_points;
+  if (npt > 0) joint_damp_kernel<<<(npt + 255) / 256, 256, 0, e->stream>>>(J.pt_data.p, npt, lambda, J.inv.p);
+  const AsmArgsJ aa{J.pair_rec.p, J.blk_data.p, J.pt_data.p, J.inv.p, J.frame_data.p, J.frame_ptr.p, J.frame_pairs.p,
+                    J.off_ptr.p, J.off_pairs.p, J.term_ptr.p, J.fe_ptr.p, J.fe_entries.p, J.sky_i.p, J.sky_j.p,
+                    e->block_point.p, J.terms.p, nullptr, nullptr, nullptr, nullptr, nf, J.n_sky, lambda};
+  joint_export_kernel<<<nf * (K + 1) + nf + 1, 64, 0, e->stream>>>(ExArgsJ{aa, J.ex_src.p, X, K, J.ex_stride});
+  PBA_HIP(hipGetLastError());
+  J.ex_lin = J.lin_id;
+  J.ex_lambda = lambda;
+  J.ex_band = K;
+  J.have_step = false;  // (inv is this export's: a step of another λ no longer has its point part)
+  return PBA_OK;
+}
+
+struct ImportParts {
+  double model_kf = 0.0, model_pt = 0.0, sq_step_kf = 0.0, sq_step_pt = 0.0, sq_x_kf = 0.0, sq_x_pt = 0.0;
+  double gmax_kf = 0.0;  // the keyframes' part of the linearisation's gradient norm, from the summed direct gradient
+  int status = 0;
+};
+
+// X holds the sum over the ranks of an export at (λ, K).  solve = false: only the summed system and the keyframes'
+// gradient norm (the LM loop's gradient test where no trial follows).
+int import_j(pba_engine* e, double lambda, int K, const double* X, bool solve, ImportParts* out) {
+  JointSolve& J = e->joint;
+  const int nf = e->n_frames, npt = e->n_points;
+  joint_import_kernel<<<J.ex_n_sky, 64, 0, e->stream>>>(ImpArgsJ{X, J.fixed.p, e->poses.p, e->affine_state.p, J.ex_sky_i.p,
+                                                                 J.ex_sky_j.p, J.ex_S.p, J.ex_L.p, J.g.p, J.ex_frame.p,
+                                                                 J.ex_gmax_f.p, J.ex_cst.p, K, J.ex_stride, lambda});
+  PBA_HIP(hipGetLastError());
+  std::vector<double> gf(nf), h;
+  int st = 0;
+  if (solve) {
+    SolveArgsJ so{J.ex_L.p, J.ex_first.p, J.ex_row.p, J.g.p, J.Linv.p, J.x.p, J.status.p, nf, J.ex_colptr.p, J.ex_colrows.p};
+    joint_solve_kernel<<<1, 256, 0, e->stream>>>(so);
+    UpdArgs ua{J.x.p, J.pt_data.p, J.blk_data.p, J.inv.p, J.ex_frame.p, e->poses.p, e->rho.p, e->affine_state.p,
+               J.pt_ptr.p, J.pt_blocks.p, e->point_host_d.p, J.status.p, e->block_rec.p, J.ex_cst.p, J.drho.p,
+               J.poses_new.p, J.rho_new.p, J.ab_new.p, J.red6.p, npt, nf, lambda};
+    joint_update_parts_kernel<<<J.upd_slots, 256, 0, e->stream>>>(ua);
+    PBA_HIP(hipGetLastError());
+    h.resize(8 * (size_t)J.upd_slots);
+    PBA_HIP(hipMemcpyAsync(&st, J.status.p, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    PBA_HIP(hipMemcpyAsync(h.data(), J.red6.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->stream));
+  }
+  PBA_HIP(hipMemcpyAsync(gf.data(), J.ex_gmax_f.p, sizeof(double) * gf.size(), hipMemcpyDeviceToHost, e->stream));
+  PBA_HIP(hipStreamSynchronize(e->stream));
+  ImportParts p;
+  for (int s = 0; solve && s < J.upd_slots; ++s) {
+    p.model_pt += h[8 * s];
+    p.sq_step_pt += h[8 * s + 1];
+    p.sq_x_pt += h[8 * s + 2];
+    p.model_kf += h[8 * s + 3];
+    p.sq_step_kf += h[8 * s + 4];
+    p.sq_x_kf += h[8 * s + 5];
+  }
+  for (double v : gf) p.gmax_kf = std::max(p.gmax_kf, v);
+  p.status = st != 0 ? 1 : 0;
+  if (solve) {
+    J.have_step = st == 0;
+    J.step_band = true;
+  }
+  *out = p;
+  return PBA_OK;
+}
+
+// the checks pba_joint_step_import and the LM loop share: the export this import follows
+int exported(pba_engine* e, double lambda, int K) {
+  const JointSolve& J = e->joint;
+  if (!J.linearized) return fail(PBA_ERR_NOT_READY, "pba_joint_linearize first");
+  if (J.ex_K != K || J.ex_lin != J.lin_id || J.ex_band != K || J.ex_lambda != lambda)
+    return fail(PBA_ERR_NOT_READY, "pba_joint_step_export at this lambda and band first");
   return PBA_OK;
 }
 
@@ -896,12 +1216,14 @@ int pba_joint_get_reduced_system(pba_engine* e, double* S_dense, double* g) {
   if (!J.linearized || !J.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
   const int nf = e->n_frames;
   const size_t n = 8 * (size_t)nf;
-  if (S_dense) {
-    std::vector<double> S((size_t)64 * J.n_sky);
-    PBA_HIP(hipMemcpyAsync(S.data(), J.S.p, sizeof(double) * S.size(), hipMemcpyDeviceToHost, e->stream));
+  if (S_dense) {  // after an import: the summed system over the band profile
+    std::vector<double> S((size_t)64 * (J.step_band ? J.ex_n_sky : J.n_sky));
+    PBA_HIP(hipMemcpyAsync(S.data(), J.step_band ? J.ex_S.p : J.S.p, sizeof(double) * S.size(), hipMemcpyDeviceToHost,
+                           e->stream));
     PBA_HIP(hipStreamSynchronize(e->stream));
     // (a diagonal block's lower triangle is what is factored)
-    skyline_to_dense<8>(S, J.first_h, J.row_h, nf, true, [](int, int, int, int, double v) { return v; }, S_dense);
+    skyline_to_dense<8>(S, J.step_band ? J.ex_first_h : J.first_h, J.step_band ? J.ex_row_h : J.row_h, nf, true,
+                        [](int, int, int, int, double v) { return v; }, S_dense);
   }
   if (g) {
     PBA_HIP(hipMemcpyAsync(g, J.g.p, sizeof(double) * n, hipMemcpyDeviceToHost, e->stream));
@@ -955,6 +1277,142 @@ int pba_solve_joint(pba_engine* e, const pba_solver_options* o, pba_solver_summa
         if (int rc = candidate_cost_j(e, cost, &nv)) return rc;
         if (nv < e->joint.n_valid) *cost = DBL_MAX;  // a failed evaluation (pba_solve's rule)
         return PBA_OK;
+      },
+      [&]() { return accept_j(e); }};
+  return host_lm(o, stages, e->gn.history, sum);
+}
+
+int pba_joint_band(pba_engine* e, int32_t* band) {
+  if (int rc = ready(e)) return rc;
+  if (!band) return fail(PBA_ERR_INVALID_ARGUMENT, "null band");
+  *band = local_band(e);
+  return PBA_OK;
+}
+
+int pba_joint_exchange_size(pba_engine* e, int32_t band, int64_t* count) {
+  if (int rc = ready(e)) return rc;
+  if (!count) return fail(PBA_ERR_INVALID_ARGUMENT, "null count");
+  if (int rc = check_band(e, band)) return rc;
+  *count = ((int64_t)(band + 1) * 64 + kJointExTail) * e->n_frames + kJointExScalars;
+  return PBA_OK;
+}
+
+int pba_joint_step_export(pba_engine* e, double lambda, int32_t band, double* d_exchange) {
+  if (int rc = ready(e)) return rc;
+  if (!(lambda >= 0.0)) return fail(PBA_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
+  if (!d_exchange) return fail(PBA_ERR_INVALID_ARGUMENT, "null exchange buffer");
+  if (int rc = check_band(e, band)) return rc;
+  if (!e->joint.linearized) return fail(PBA_ERR_NOT_READY, "pba_joint_linearize first");
+  return export_j(e, lambda, band, d_exchange);
+}
+
+int pba_joint_step_import(pba_engine* e, double lambda, int32_t band, const double* d_exchange, double* model_keyframes,
+                          double* model_points, int32_t* solver_status) {
+  if (int rc = ready(e)) return rc;
+  if (!(lambda >= 0.0)) return fail(PBA_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
+  if (!d_exchange) return fail(PBA_ERR_INVALID_ARGUMENT, "null exchange buffer");
+  if (int rc = check_band(e, band)) return rc;
+  if (int rc = exported(e, lambda, band)) return rc;
+  ImportParts p;
+  if (int rc = import_j(e, lambda, band, d_exchange, true, &p)) return rc;
+  if (solver_status) *solver_status = p.status;
+  if (model_keyframes) *model_keyframes = p.status == 0 ? 0.5 * p.model_kf : 0.0;
+  if (model_points) *model_points = p.status == 0 ? 0.5 * p.model_pt : 0.0;
+  return PBA_OK;
+}
+
+// pba_solve_joint's loop over all ranks: host_lm with the stages below.  One sum of the scalar slots per linearisation,
+// and per trial the sum of the system, then of the scalar slots.  What decides — cost, valid blocks, model decrease,
+// norms, the solve's status, the gradient test — is either a sum over the ranks or computed by every rank from the
+// summed buffer, so every rank takes the same decisions and none is exchanged.
+// The gradient norm: max(the keyframes' part, this rank's points).  The keyframes' part needs the summed direct
+// gradient, which a linearisation has only once its first trial has summed the system, so the value reported with a
+// linearisation carries the keyframes' part of the last summed system.  The gradient-tolerance stop does not rest on
+// that: it can apply only where no rank holds a point above the tolerance (slot 3 sums to 0), and there every rank
+// exports at λ = 0 and the system is summed once more for this linearisation's own keyframe part.
+int pba_solve_joint_distributed(pba_engine* e, const pba_solver_options* o, int32_t band, double* d_exchange,
+                                pba_allreduce_fn allreduce, void* user, pba_solver_summary* sum) {
+  if (int rc = ready(e)) return rc;
+  if (!d_exchange || !allreduce) return fail(PBA_ERR_INVALID_ARGUMENT, "null exchange buffer or allreduce");
+  if (int rc = check_band(e, band)) return rc;
+  if (int rc = ensure_exchange(e, band)) return rc;
+  JointSolve& J = e->joint;
+  const int K = band;
+  const long long nx = J.ex_scalar_off;
+  double* const Y = d_exchange + nx;
+  const double gtol = o ? o->gradient_tolerance : 1e-10;
+  auto reduce = [&](double* buf, long long n) {  // the host callback: after the stream has drained, complete on return
+    PBA_HIP(hipStreamSynchronize(e->stream));
+    if (int rc = allreduce(user, buf, n)) return fail(PBA_ERR_DEVICE, "allreduce callback failed (" + std::to_string(rc) + ")");
+    return (int)PBA_OK;
+  };
+  auto reduce_scalars = [&](double (&v)[kJointExScalars]) {
+    PBA_HIP(hipMemcpyAsync(Y, v, sizeof v, hipMemcpyHostToDevice, e->stream));
+    if (int rc = reduce(Y, kJointExScalars)) return rc;
+    PBA_HIP(hipMemcpyAsync(v, Y, sizeof v, hipMemcpyDeviceToHost, e->stream));
+    PBA_HIP(hipStreamSynchronize(e->stream));
+    return (int)PBA_OK;
+  };
+  double n_valid = 0.0;            // Σ over the ranks, of the current linearisation
+  double sq_x_kf = 0.0, sq_x_pt = 0.0;  // ‖candidate‖² of the last step: the keyframes', this rank's points'
+  double gmax_kf = 0.0;            // the keyframes' part of the gradient norm, of the last summed system
+  double cand = 0.0, cand_valid = 0.0;
+  HostLmStages stages{
+      [&](double* cost, double* gmax, double* x_norm) {
+        double c = 0.0, gp = 0.0;
+        if (int rc = linearize_j(e, &c)) return rc;
+        std::vector<double> p(2 * (size_t)std::max(J.pt_slots, 1), 0.0);
+        if (J.pt_slots > 0) {
+          PBA_HIP(hipMemcpyAsync(p.data(), J.gmax_p.p, sizeof(double) * 2 * (size_t)J.pt_slots, hipMemcpyDeviceToHost, e->stream));
+          PBA_HIP(hipStreamSynchronize(e->stream));
+        }
+        double above = 0.0;  // this rank's point groups (joint_point_kernel's workgroups) with an entry above the tolerance
+        for (int s = 0; s < J.pt_slots; ++s) {
+          gp = std::max(gp, p[2 * s + 1]);
+          above += p[2 * s + 1] > gtol ? 1.0 : 0.0;
+        }
+        double v[kJointExScalars] = {c, J.n_valid, sq_x_pt, above};
+        if (int rc = reduce_scalars(v)) return rc;
+        *cost = v[0];
+        n_valid = v[1];
+        *x_norm = std::sqrt(sq_x_kf + v[2]);
+        if (v[3] == 0.0) {  // no point above the tolerance on any rank: the keyframes decide
+          if (int rc = export_j(e, 0.0, K, d_exchange)) return rc;
+          if (int rc = reduce(d_exchange, nx)) return rc;
+          ImportParts ip;
+          if (int rc = import_j(e, 0.0, K, d_exchange, false, &ip)) return rc;
+          gmax_kf = ip.gmax_kf;
+        }
+        double g = std::max(gmax_kf, gp);
+        if (v[3] > 0.0 && !(g > gtol)) g = std::nextafter(gtol, DBL_MAX);  // (above the tolerance on another rank)
+        *gmax = g;
+        return (int)PBA_OK;
+      },
+      [&](double lambda, int* status, double* model, double* sq_step) {
+        if (int rc = export_j(e, lambda, K, d_exchange)) return rc;
+        if (int rc = reduce(d_exchange, nx)) return rc;
+        ImportParts ip;
+        if (int rc = import_j(e, lambda, K, d_exchange, true, &ip)) return rc;
+        gmax_kf = ip.gmax_kf;
+        *status = ip.status;
+        *model = 0.0;
+        *sq_step = 0.0;
+        if (ip.status != 0) return (int)PBA_OK;  // (the same status on every rank: none sums the scalars)
+        double c = 0.0, nv = 0.0;
+        if (int rc = candidate_cost_j(e, &c, &nv)) return rc;
+        double v[kJointExScalars] = {ip.model_pt, c, nv, ip.sq_step_pt, ip.sq_x_pt};
+        if (int rc = reduce_scalars(v)) return rc;
+        *model = 0.5 * (ip.model_kf + v[0]);
+        cand = v[1];
+        cand_valid = v[2];
+        *sq_step = ip.sq_step_kf + v[3];
+        sq_x_kf = ip.sq_x_kf;
+        sq_x_pt = ip.sq_x_pt;
+        return (int)PBA_OK;
+      },
+      [&](double* cost) {
+        *cost = cand_valid < n_valid ? DBL_MAX : cand;  // a failed evaluation (pba_solve's rule), over all ranks
+        return (int)PBA_OK;
       },
       [&]() { return accept_j(e); }};
   return host_lm(o, stages, e->gn.history, sum);

@@ -82,5 +82,36 @@ bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
   return true;
 }
 
+int joint_local_band(const std::vector<int>& first) {
+  int band = 0;
+  for (int i = 0; i < (int)first.size(); ++i) band = std::max(band, i - first[i]);
+  return band;
+}
+
+bool build_joint_exchange(const std::vector<int>& first, const std::vector<int>& row, int K, JointExchangePlan& X) {
+  const int nf = (int)first.size();
+  if (nf <= 0 || (int)row.size() != nf + 1 || K < joint_local_band(first) || K > nf - 1) return false;
+  X.K = K;
+  X.stride = (long long)(K + 1) * 64 + kJointExTail;
+  X.scalar_off = X.stride * nf;
+  X.count = X.scalar_off + kJointExScalars;
+  X.src.assign((size_t)nf * (K + 1), -1);
+  X.first.resize(nf);
+  for (int i = 0; i < nf; ++i) {
+    X.first[i] = std::max(0, i - K);
+    for (int j = first[i]; j <= i; ++j) X.src[(size_t)i * (K + 1) + (j - (i - K))] = row[i] + (j - first[i]);
+  }
+  skyline_profile(X.first, X.row, X.last, X.colptr, X.colrows);
+  X.n_sky = X.row[nf];
+  X.sky_i.resize(X.n_sky);
+  X.sky_j.resize(X.n_sky);
+  for (int i = 0; i < nf; ++i)
+    for (int j = X.first[i]; j <= i; ++j) {
+      X.sky_i[X.row[i] + (j - X.first[i])] = i;
+      X.sky_j[X.row[i] + (j - X.first[i])] = j;
+    }
+  return true;
+}
+
 }  // namespace detail
 }  // namespace pba

@@ -47,5 +47,29 @@ struct JointPlan {
 // its host (the plan is then unspecified)
 bool build_joint_plan(const JointPlanInput& in, JointPlan& P);
 
+// The exchange of the multi-GPU joint solve (pba.h pba_joint_step_export / import): every rank's reduced system goes
+// into one banded layout of K block rows, any K with joint_local_band ≤ K ≤ n_frames − 1, and the sum over the ranks is
+// factored over the band's own profile.
+//   Layout (doubles): per keyframe i, (K + 1) row-major 8×8 blocks, block c = column i − K + c, then a tail of
+//   kJointExTail doubles [g_S(8) | g_direct(8) | diag(8) | valid blocks on the keyframe | 0 …]: `stride` per keyframe;
+//   after the keyframes kJointExScalars scalar slots at `scalar_off`; `count` in all.
+//   src[i·(K + 1) + c]: the local skyline block (its direct and Schur lists are JointPlan's) that fills exchange block
+//   (i, c), or −1 where the exchange block is zeros: left of column 0, or outside the local profile.
+//   first … colrows, n_sky: the band profile first[i] = max(0, i − K) (skyline_profile), sky_i / sky_j its blocks'
+//   keyframes.
+constexpr int kJointExTail = 32;
+constexpr int kJointExScalars = 16;
+struct JointExchangePlan {
+  int K = -1, n_sky = 0;
+  long long stride = 0, scalar_off = 0, count = 0;
+  std::vector<int> src;
+  std::vector<int> first, row, last, colptr, colrows, sky_i, sky_j;
+};
+
+// the local bandwidth in block rows: max over i of i − first[i]
+int joint_local_band(const std::vector<int>& first);
+// first, row: a JointPlan's.  false (X unspecified) when K is below the local band or above n_frames − 1.
+bool build_joint_exchange(const std::vector<int>& first, const std::vector<int>& row, int K, JointExchangePlan& X);
+
 }  // namespace detail
 }  // namespace pba

@@ -168,3 +168,25 @@ def solve_distributed(engine, group=None, device=None, comm=None, **options) -> 
     ar = TorchAllReduce(engine.gn_exchange_size(band), device if device is not None else "cpu", group)
     engine.set_rank(dist.get_rank(group))  # rank 0's pose part decides on every rank (pba_gn_set_rank)
     return engine.solve_distributed(band, ar.ptr, ar, **options)
+
+
+def solve_joint_distributed(engine, group=None, device=None, **options) -> dict:
+    """The joint LM of poses, inverse distances and (a, b) over all ranks of `group` (pba_solve_joint_distributed):
+    collective, every rank calls it.  The band is agreed by a max all-reduce as in `global_band`; the collective is the
+    TorchAllReduce callback (the joint loop is host-driven).  Every rank's shard needs at least one block: if a rank has
+    none, every rank raises (the caller chooses other keyframe ranges)."""
+    import torch
+    import torch.distributed as dist
+    if device is not None:
+        device = torch.device(device)
+    dev = device if device is not None and dist.get_backend(group) == "nccl" else "cpu"
+    empty = engine.n_blocks == 0
+    t = torch.tensor([0 if empty else engine.joint_band(), int(empty)], dtype=torch.int64, device=dev)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    if int(t[1].item()):
+        raise ValueError("solve_joint_distributed: a rank's shard has no blocks"
+                         + (" (this rank's)" if empty else "")
+                         + "; choose host-keyframe ranges (shard_problem's bounds) with at least one block per rank")
+    band = int(t[0].item())
+    ar = TorchAllReduce(engine.joint_exchange_size(band), device if device is not None else "cpu", group)
+    return engine.solve_joint_distributed(band, ar.ptr, ar, **options)

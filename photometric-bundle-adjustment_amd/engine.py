@@ -213,6 +213,13 @@ def lib(path: Optional[str] = None):
         "pba_joint_candidate_cost": ([vp, C.POINTER(C.c_double)], C.c_int),
         "pba_joint_accept": ([vp], C.c_int),
         "pba_solve_joint": ([vp, C.POINTER(SolverOptions), C.POINTER(SolverSummary)], C.c_int),
+        "pba_joint_band": ([vp, C.POINTER(i32)], C.c_int),
+        "pba_joint_exchange_size": ([vp, i32, C.POINTER(C.c_int64)], C.c_int),
+        "pba_joint_step_export": ([vp, C.c_double, i32, vp], C.c_int),
+        "pba_joint_step_import": ([vp, C.c_double, i32, vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                   C.POINTER(i32)], C.c_int),
+        "pba_solve_joint_distributed": ([vp, C.POINTER(SolverOptions), i32, vp, ALLREDUCE_FN, vp,
+                                         C.POINTER(SolverSummary)], C.c_int),
         "pba_gn_system_size": ([vp, C.POINTER(i32)], C.c_int),
         "pba_gn_set_rank": ([vp, i32], C.c_int),
         "pba_compute_projections": ([vp, i32, vp, vp, vp, vp, C.POINTER(OutlierThresholds), vp, vp, vp, vp], C.c_int),
@@ -721,6 +728,49 @@ class Engine:
         o = solver_options(**options)
         s = SolverSummary()
         self._ck(self._L.pba_solve_joint(self._h, C.byref(o), C.byref(s)), "pba_solve_joint")
+        return s.as_dict()
+
+    # -- the joint solve over several GPUs (include/pba.h; host driver in distributed.py) ----------------
+    def joint_band(self) -> int:
+        b = C.c_int32()
+        self._ck(self._L.pba_joint_band(self._h, C.byref(b)), "pba_joint_band")
+        return b.value
+
+    def joint_exchange_size(self, band: int) -> int:
+        n = C.c_int64()
+        self._ck(self._L.pba_joint_exchange_size(self._h, band, C.byref(n)), "pba_joint_exchange_size")
+        return n.value
+
+    def joint_step_export(self, lam: float, band: int, exchange_ptr: int):
+        self._ck(self._L.pba_joint_step_export(self._h, lam, band, C.c_void_p(exchange_ptr)), "pba_joint_step_export")
+
+    def joint_step_import(self, lam: float, band: int, exchange_ptr: int):
+        """(model decrease: the keyframes' part, this rank's points' part; solver status)"""
+        mk, mp, st = C.c_double(), C.c_double(), C.c_int32()
+        self._ck(self._L.pba_joint_step_import(self._h, lam, band, C.c_void_p(exchange_ptr), C.byref(mk), C.byref(mp),
+                                             C.byref(st)), "pba_joint_step_import")
+        return mk.value, mp.value, st.value
+
+    def solve_joint_distributed(self, band: int, exchange_ptr: int, allreduce, **options) -> dict:
+        """pba_solve_joint_distributed; `allreduce(ptr, count)` as for solve_distributed."""
+        err = []
+
+        def cb(_user, ptr, count):
+            try:
+                allreduce(ptr, count)
+                return 0
+            except BaseException as ex:  # surfaced after the C call returns
+                err.append(ex)
+                return 1
+
+        fn = ALLREDUCE_FN(cb)
+        o = solver_options(**options)
+        s = SolverSummary()
+        rc = self._L.pba_solve_joint_distributed(self._h, C.byref(o), band, C.c_void_p(exchange_ptr), fn, None,
+                                                 C.byref(s))
+        if err:
+            raise err[0]
+        _check(rc, "pba_solve_joint_distributed")
         return s.as_dict()
 
     def set_affine_state(self, ab: np.ndarray):
