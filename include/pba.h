@@ -124,7 +124,8 @@ int pba_synchronize(pba_engine* engine);
 /* Results ---------------------------------------------------------------------------------------- */
 /* values per record as pba_get_records returns them: 14·R, or — with pba_set_optimize_intrinsics, on geometric and
  * photometric engines alike — 22·R: [ r(R) | J_host(R×6) | J_target(R×6) | J_rho(R) | J_intr(R×8) ], or — with
- * pba_set_affine_brightness — 18·R: [ … | J_rho(R) | J_ab_host(R×2) | J_ab_target(R×2) ] */
+ * pba_set_affine_brightness — 18·R: [ … | J_rho(R) | J_ab_host(R×2) | J_ab_target(R×2) ], or — with both, which
+ * pba_set_intrinsics_with_affine allows — 26·R: [ … | J_rho(R) | J_intr(R×8) | J_ab_host(R×2) | J_ab_target(R×2) ] */
 int pba_record_floats(const pba_engine* engine);
 /* Record storage format (photometric engines): PBA_RECORD_F32 (default) or PBA_RECORD_F16 — IEEE half records,
  * half the HBM write traffic (config C5's "fp16 residuals"; evaluation stays fp64 warp + fp32 chain, rounding
@@ -152,7 +153,8 @@ int pba_set_record_format(pba_engine* engine, int32_t format);
 int pba_record_format(const pba_engine* engine);
 /* device bytes per record as stored: 4·pba_record_floats (PBA_RECORD_F32), 28·R (PBA_RECORD_F16) or 30·R
  * (PBA_RECORD_F16_SCALED).  pba_record_floats stays 14·R in the half formats: it describes what pba_get_records returns.
- * With pba_set_optimize_intrinsics the records are fp32 only: 88·R bytes; with pba_set_affine_brightness 72·R. */
+ * With pba_set_optimize_intrinsics the records are fp32 only: 88·R bytes; with pba_set_affine_brightness 72·R; with
+ * both (pba_set_intrinsics_with_affine) 104·R. */
 int pba_record_bytes(const pba_engine* engine);
 /* Target-intrinsics Jacobian (geometric and photometric engines; BundleAdjustmentOptions::optimize_intrinsics,
  * map_utils.h:339-345):
@@ -215,7 +217,8 @@ int pba_get_intrinsics(pba_engine* engine, double* intrinsics);
  * pba_set_affine_brightness: enabling sets the state to zeros, disabling restores the 14·R records.  Refused with
  * PBA_ERR_INVALID_ARGUMENT, the engine left as it was: on a geometric engine; with a half record format active (and
  * pba_set_record_format then refuses the half formats: the brightness columns have no half layout); together with
- * pba_set_optimize_intrinsics, whichever comes second (a 26-column record is not built).  While it is enabled, and
+ * pba_set_optimize_intrinsics, whichever comes second, unless pba_set_intrinsics_with_affine (below) has opted in to
+ * the 26-column record.  While it is enabled, and
  * unless pba_gn_set_solve_affine (below) opts in, every on-device Gauss-Newton entry point (pba_gn_*, pba_solve,
  * pba_solve_pyramid, pba_gn_step_export/import, pba_solve_distributed(_comm)) returns PBA_ERR_INVALID_ARGUMENT instead
  * of solving with a = b = 0.  The consumer of the brightness columns is an outer solver over the records
@@ -228,6 +231,31 @@ int pba_set_affine_brightness(pba_engine* engine, int32_t enable);
 int pba_set_affine_state(pba_engine* engine, const double* ab);
 int pba_set_affine_state_device(pba_engine* engine, const double* d_ab);
 int pba_get_affine_state(pba_engine* engine, double* ab);
+/* Free intrinsics together with affine brightness (photometric engines): the records of the full photometric problem —
+ * poses, inverse distances, intrinsics (BundleAdjustmentOptions::optimize_intrinsics, map_utils.h:339-345) and (a, b) —
+ * for an outer solver (include/pba_ceres.h, GpuPhotometricAffineIntrinsicsCost).
+ * Default 0: pba_set_optimize_intrinsics and pba_set_affine_brightness refuse each other as described above.  With
+ * enable = 1 each accepts the other, in either order; the switch alone changes no record, size or evaluation.  With
+ * both on, pba_record_floats = 26·R and pba_record_bytes = 104·R (fp32 only):
+ *   [ r(R) | J_host(R×6) | J_target(R×6) | J_rho(R) | J_intr(R×8) | J_ab_host(R×2) | J_ab_target(R×2) ]
+ *   r_k = (I_t(π_state(p̃_k)) − b_t) − E·(I_h,k − b_h): the target projects with the intrinsics state, the host
+ *   unprojects with the cameras' values, E = exp(a_t − a_h) in fp64 once per block;
+ *   J_intr row k = ∇I_t·∂π/∂k, exact zeros for parameters the model does not use (∇I_t does not depend on (a, b));
+ *   J_ab_host row k = [ E·(I_h,k − b_h), E ],  J_ab_target row k = [ −E·(I_h,k − b_h), −1 ].
+ * Turning one of the two off gives the other's 22·R or 18·R record back.  Everything else is as with one switch:
+ * validity (and a non-finite a, pose or intrinsics-state value — one that leaves π not finite — makes the blocks it
+ * touches invalid), 26·R zeros for an invalid block, the per-block Huber cost on the new r, a residual-only evaluation writing
+ * r at the 26·R stride, pba_set_frames* zeroing (a, b), the intrinsics state starting at the cameras' values, J_intr
+ * with respect to the level-0 state at every pyramid level and no level factor on (a, b); every read-back path serves
+ * the 26·R records (pba_get_records, _raw, _async / pba_wait_records, pba_get_residuals, pba_device_records,
+ * pba_decode_records_device), and pba_set_record_format keeps refusing the half formats while either switch is on.
+ * With both on, every on-device solve entry point returns PBA_ERR_INVALID_ARGUMENT and changes nothing, whatever
+ * pba_gn_set_solve_intrinsics and pba_gn_set_solve_affine say: pba_gn_*, pba_solve, pba_solve_pyramid,
+ * pba_gn_step_export/import, pba_solve_distributed(_comm), pba_affine_*, pba_solve_affine, pba_joint_*,
+ * pba_solve_joint, pba_joint_step_export/import and pba_solve_joint_distributed.
+ * PBA_ERR_INVALID_ARGUMENT, the engine left as it was: on a geometric engine; for enable = 1 with a half record format
+ * active; for enable = 0 while both switches are on (turn one off first). */
+int pba_set_intrinsics_with_affine(pba_engine* engine, int32_t enable);
 /* Photometric engines with pba_set_affine_brightness: enable = 1 makes the single-GPU on-device solve
  * (pba_gn_linearize/step/candidate_cost/accept, pba_gn_get_reduced_system/get_step, pba_solve, pba_solve_pyramid) run
  * with the residual above at the engine's affine state, which those calls hold constant — Ceres'

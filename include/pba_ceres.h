@@ -33,7 +33,12 @@
 //     pba_set_affine_brightness and uploads the blocks' current values before every evaluation (pba_set_affine_state);
 //     r_k = (I_t − b_t) − exp(a_t − a_h)·(I_h,k − b_h), and the records' tail J_ab_host, J_ab_target (R×2 each) is what
 //     GpuPhotometricAffineCost<P> hands to Ceres for its fourth and fifth parameter blocks.  Without the blocks a
-//     Jacobian request for one of them is refused like an intrinsics one.  Not combined with the intrinsics blocks.
+//     Jacobian request for one of them is refused like an intrinsics one.
+//   * Both (photometric): given the intrinsics blocks and the (a, b) blocks, the evaluator first calls
+//     pba_set_intrinsics_with_affine, then both switches, and uploads both states before every evaluation; the records
+//     are 26·R values [… | J_rho | J_intr | J_ab_host | J_ab_target], which GpuPhotometricAffineIntrinsicsCost<P> hands
+//     to Ceres for its fourth, fifth and sixth parameter blocks: the full photometric problem of poses, inverse
+//     distances, intrinsics and brightness under ceres::Solve.
 //
 // The loss function stays with Ceres (HuberLoss is applied after Evaluate, residual_block.cc:161-196).
 // Requires <ceres/ceres.h> (Ceres ≥ 2.0, which has EvaluationCallback) and include/pba.h on the include path.
@@ -189,7 +194,8 @@ class GpuEvaluator : public ceres::EvaluationCallback {
   // problem's intrinsics blocks may be free (optimize_intrinsics; geometric or photometric engine), else empty.  The
   // engine must already hold the problem structure.
   // affine[f] = the (a_f, b_f) block of keyframe f (2 doubles) when the photometric problem carries affine brightness
-  // blocks (GpuPhotometricAffineCost), else empty; one per keyframe, not together with `intrinsics`.
+  // blocks (GpuPhotometricAffineCost), else empty; one per keyframe.  Together with `intrinsics` (a photometric engine):
+  // the 26-column records of GpuPhotometricAffineIntrinsicsCost.
   GpuEvaluator(pba_engine* engine, std::vector<double*> poses, std::vector<double*> inv_dist,
                std::vector<double*> intrinsics = {}, PoseJacobian pose_jacobian = PoseJacobian::kReferenceSE3,
                std::vector<double*> affine = {})
@@ -199,6 +205,8 @@ class GpuEvaluator : public ceres::EvaluationCallback {
       throw std::runtime_error("pba_ceres: fp16 records saturate at ±65504; the adapter needs PBA_RECORD_F32");
     if (!ab_.empty() && ab_.size() != poses_.size())
       throw std::runtime_error("pba_ceres: one affine brightness block per keyframe");
+    if (!intr_.empty() && !ab_.empty())  // the two switches accept each other only after this opt-in
+      check(pba_set_intrinsics_with_affine(engine_, 1), "pba_set_intrinsics_with_affine");
     if (!intr_.empty()) check(pba_set_optimize_intrinsics(engine_, 1), "pba_set_optimize_intrinsics");
     if (!ab_.empty()) check(pba_set_affine_brightness(engine_, 1), "pba_set_affine_brightness");
     R_ = pba_residuals_per_block(engine_);
@@ -215,7 +223,7 @@ class GpuEvaluator : public ceres::EvaluationCallback {
 
   // Called on the solver thread after Ceres has written the evaluation point into the user's parameter memory
   // (program_evaluator.h:157-162).  A Jacobian evaluation reads back the whole records; a residual-only one (the
-  // LM candidate, trust_region_minimizer.cc:761-779) only the residuals, R of every 14R (22R, 18R) record values.  The
+  // LM candidate, trust_region_minimizer.cc:761-779) only the residuals, R of every 14R (22R, 18R, 26R) record values.  The
   // evaluation after an accepted step comes with new_evaluation_point = false (trust_region_minimizer.cc:805-822):
   // when the point was already evaluated with Jacobians nothing is recomputed.
   // Where PrepareForEvaluation's time goes (seconds, summed over calls; [0] residual-only, [1] with Jacobians):
@@ -461,6 +469,40 @@ class GpuPhotometricAffineCost : public ceres::SizedCostFunction<P, 7, 7, 1, 2, 
     for (int q = 0; q < 2; ++q)
       if (jacobians[3 + q])
         for (int i = 0; i < 2 * P; ++i) jacobians[3 + q][i] = rec[(14 + 2 * q) * P + i];
+    return true;
+  }
+
+ private:
+  const GpuEvaluator* ev_;
+  int block_, host_, target_;
+};
+
+// Photometric block with free target intrinsics and affine brightness: SizedCostFunction<P, 7, 7, 1, 8, 2, 2> over
+// (T_w_host, T_w_target, ρ, intr_target, ab_host, ab_target), the 26·P-value records of an evaluator that was given both
+// the intrinsics and the (a, b) blocks.  jacobians[3] = J_intr (P×8 row-major, record columns 14·P…), jacobians[4] =
+// J_ab_host (P×2, columns 22·P…) and jacobians[5] = J_ab_target (P×2, columns 24·P…); any of them may be null (a constant
+// block), which leaves the others unchanged.  A request for jacobians[3] without the intrinsics blocks, or for
+// jacobians[4] or [5] without the (a, b) blocks, and only that, is refused (refused_intrinsics(), refused_affine()).
+template <int P>
+class GpuPhotometricAffineIntrinsicsCost : public ceres::SizedCostFunction<P, 7, 7, 1, 8, 2, 2> {
+ public:
+  GpuPhotometricAffineIntrinsicsCost(const GpuEvaluator* ev, int block, int host, int target)
+      : ev_(ev), block_(block), host_(host), target_(target) {}
+  bool Evaluate(double const* const* /*parameters*/, double* residuals, double** jacobians) const override {
+    if (jacobians && (jacobians[4] || jacobians[5]) && !ev_->has_affine()) {
+      ev_->refuse_affine();
+      return false;
+    }
+    // (copy_block refuses jacobians[3] without the intrinsics blocks and writes it from columns 14·P…)
+    if (!copy_block<P>(*ev_, block_, host_, target_, residuals, jacobians, 8)) return false;
+    if (!jacobians) return true;
+    // the brightness blocks sit behind J_intr only in the 26·P records; an evaluator without the intrinsics blocks
+    // serves 18·P records with them at 14·P (jacobians[3] is null here, or copy_block has refused)
+    const int c0 = ev_->has_intrinsics() ? 22 : 14;
+    const float* rec = ev_->record(block_);
+    for (int q = 0; q < 2; ++q)
+      if (jacobians[4 + q])
+        for (int i = 0; i < 2 * P; ++i) jacobians[4 + q][i] = rec[(c0 + 2 * q) * P + i];
     return true;
   }
 

@@ -328,6 +328,8 @@ int ready(pba_engine* e) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
   if (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC || !e->affine)
     return fail(PBA_ERR_INVALID_ARGUMENT, "the brightness solve needs a photometric engine with pba_set_affine_brightness");
+  // its kernels read 18-column brightness columns and project with the cameras: not the 26-column engine's residual
+  if (int rc = solve_refuses_both(e)) return rc;
   if (e->n_blocks <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_blocks first");
   if (!e->state_set) return fail(PBA_ERR_NOT_READY, "pba_set_state first");
   if (!e->have_images || e->P <= 0) return fail(PBA_ERR_NOT_READY, "images/pattern missing");

@@ -280,8 +280,9 @@ int pba_set_optimize_intrinsics(pba_engine* e, int32_t enable) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
   if (enable && e->record_format != PBA_RECORD_F32)
     return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics need PBA_RECORD_F32 records (J_intr has no half format)");
-  if (enable && e->affine)
-    return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics and affine brightness are not combined (no 26-column record)");
+  if (enable && e->affine && !e->intr_with_affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT,
+                "free intrinsics and affine brightness are not combined without pba_set_intrinsics_with_affine");
   if (enable && e->n_cams <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_cameras first");
   if (int rc = check_device(e)) return rc;
   const bool on = enable != 0;
@@ -313,8 +314,9 @@ int pba_set_affine_brightness(pba_engine* e, int32_t enable) {
     return fail(PBA_ERR_INVALID_ARGUMENT, "affine brightness is photometric only");
   if (enable && e->record_format != PBA_RECORD_F32)
     return fail(PBA_ERR_INVALID_ARGUMENT, "affine brightness needs PBA_RECORD_F32 records (no half format)");
-  if (enable && e->opt_intr)
-    return fail(PBA_ERR_INVALID_ARGUMENT, "affine brightness and free intrinsics are not combined (no 26-column record)");
+  if (enable && e->opt_intr && !e->intr_with_affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT,
+                "affine brightness and free intrinsics are not combined without pba_set_intrinsics_with_affine");
   if (int rc = check_device(e)) return rc;
   const bool on = enable != 0;
   if (on)
@@ -324,6 +326,21 @@ int pba_set_affine_brightness(pba_engine* e, int32_t enable) {
   e->evaluated = false;
   e->res_fresh = false;
   if (e->n_blocks > 0) PBA_HIP(e->out.resize((size_t)e->n_blocks * e->rec_floats()));
+  return PBA_OK;
+}
+
+// The opt-in that lets pba_set_optimize_intrinsics and pba_set_affine_brightness accept each other, in either order
+// (26-column records [… | J_intr | J_ab_host | J_ab_target], pba_record.h).  Off, the default, the two refuse each other
+// as they did before it existed.  The switch alone changes no record, size or evaluation.
+int pba_set_intrinsics_with_affine(pba_engine* e, int32_t enable) {
+  if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
+  if (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics with affine brightness is photometric only");
+  if (enable && e->record_format != PBA_RECORD_F32)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "free intrinsics with affine brightness needs PBA_RECORD_F32 records");
+  if (!enable && e->opt_intr && e->affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT, "both switches are on: turn one of them off first");
+  e->intr_with_affine = enable != 0;
   return PBA_OK;
 }
 

@@ -25,7 +25,8 @@ using namespace pba::detail;
 
 namespace {
 
-// PM = camera model + 4 · interpolator; T = float, _Float16, ScaledF16, IntrF32 or AffineF32 (RecFormat)
+// PM = camera model + 4 · interpolator; T = float, _Float16, ScaledF16, IntrF32, AffineF32 or IntrAffineF32 (RecFormat;
+// the last stages 32·26·8·4 = 26,624 B)
 template <int PM, int LPB, int MODE, class T>
 __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const KernelArgs a) {
   constexpr int BPW = kBlockThreads / LPB;  // blocks per workgroup
@@ -62,9 +63,10 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
   if constexpr (AFF) af = block_affine(a, live ? blk : a.n_blocks - 1);
   __syncthreads();
   constexpr bool INTR = JAC && RecFormat<T>::kIntr;
+  constexpr bool PFIN = RecFormat<T>::kIntr && AFF;  // the 26-column records: a non-finite projection is invalid
   float ji[8];
   // dead lanes evaluate a staged block, masked by act
-  const Row row = photometric_row<PM, JAC, TileBlock, false, INTR, AFF>(a, s_tb[lb], off, Ih, nullptr, ji, &af);
+  const Row row = photometric_row<PM, JAC, TileBlock, false, INTR, AFF, PFIN>(a, s_tb[lb], off, Ih, nullptr, ji, &af);
   // per-block validity (ballot over the wave: the block's LPB lanes are an aligned bit field) and ‖r‖²
   const int ok = group_all<LPB>(act ? row.ok : 1);
   const float s = group_sum<LPB>(act ? row.r * row.r : 0.0f);
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
       }
       stage_intr(s_rec, P, k, ji);
     }
-    if constexpr (AFF) stage_affine(s_rec, P, k, af.E * (Ih - af.bh), af.E, ok != 0);
+    if constexpr (AFF) stage_affine<RecFormat<T>::kIntr>(s_rec, P, k, af.E * (Ih - af.bh), af.E, ok != 0);
   }
   __syncthreads();
   const int nblk = min(BPW, a.n_blocks - blk0);
@@ -152,6 +154,9 @@ constexpr int kMultiThreads = 32 * RecFormat<T>::kCols * 8 * PPL * (int)sizeof(t
 // 17–32 px run 128 threads (kMultiThreads) and never take the camera-table form.
 // KB4 with affine brightness: held to 168 VGPRs its rows spilled 24–128 B per lane (the table-free form takes 182–198),
 // so that camera-table form is compiled for 2 waves per SIMD.
+// The 26-column records (IntrAffineF32) never take the camera-table form: 26,624·PPL B of stage for 32 blocks plus their
+// tile blocks is past 60 KiB at every PPL ≥ 2, so kMultiThreads gives them 128 threads (16·104·P + 16·352 B of dynamic
+// LDS: 58,880 B at 32 px).
 template <int PPL, class T>
 constexpr int kMultiWaves =
     RecFormat<T>::kIntr || RecFormat<T>::kAffine ? 3 : (RecFormat<T>::kScaled && PPL != 3 ? 5 : 6);
@@ -213,9 +218,10 @@ void photometric_block_kernel_multi(const KernelArgs a) {
     const int px = k + LPB * j;
     const bool act = live && px < P;
     constexpr bool INTR = JAC && RecFormat<T>::kIntr;
+    constexpr bool PFIN = RecFormat<T>::kIntr && AFF;  // the 26-column records: a non-finite projection is invalid
     float ji[8];
     const Row row =  // masked by act
-        photometric_row<PM, JAC, TB, C1, INTR, AFF>(a, s_tb[lb], s_pat[px < P ? px : 0], ih, s_cam, ji, &af);
+        photometric_row<PM, JAC, TB, C1, INTR, AFF, PFIN>(a, s_tb[lb], s_pat[px < P ? px : 0], ih, s_cam, ji, &af);
     okl &= act ? row.ok : 1;
     s += act ? row.r * row.r : 0.0f;
     if constexpr (JAC && RecFormat<T>::kScaled) stage_row_scaled(s_rec, lb, P, px, row, act);
@@ -224,7 +230,7 @@ void photometric_block_kernel_multi(const KernelArgs a) {
       if (act) stage_intr(s_rec, P, px, ji);
     }
     if constexpr (JAC && AFF) {
-      if (act) stage_affine(s_rec, P, px, af.E * (ih - af.bh), af.E, true);
+      if (act) stage_affine<RecFormat<T>::kIntr>(s_rec, P, px, af.E * (ih - af.bh), af.E, true);
     }
     return row.r;
   };
@@ -284,7 +290,7 @@ void photometric_block_kernel_multi(const KernelArgs a) {
         const float z[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         stage_intr(s_rec, P, px, z);
       }
-      if constexpr (AFF) stage_affine(s_rec, P, px, 0.0f, 0.0f, false);
+      if constexpr (AFF) stage_affine<RecFormat<T>::kIntr>(s_rec, P, px, 0.0f, 0.0f, false);
     }
   }
   __syncthreads();
@@ -435,13 +441,16 @@ void launch_geometric(pba_engine* e, const KernelArgs& ka, int mode) {
 // The record format T and the compile-time mode M (1 records, 0 residuals, 2 costs only) of a photometric launch, from
 // the engine's state: calls fn(Tag<T>, Mode<M>).  The first row that holds:
 //   engine state                                    modes 1 and 0   mode 2
+//   affine brightness and free intrinsics           IntrAffineF32   AffineF32
 //   affine brightness                               AffineF32       AffineF32
 //   free intrinsics                                 IntrF32         float
 //   PBA_RECORD_F16_SCALED                           ScaledF16       float
 //   PBA_RECORD_F16                                  _Float16        float
 //   PBA_RECORD_F32                                  float           float
-// (the half formats are refused with free intrinsics and with affine brightness, and those two with each other.)  A
-// cost-only launch stores no record, so only the affine residual — another residual — has a kernel of its own for it.
+// (the half formats are refused with free intrinsics and with affine brightness, and those two with each other unless
+// pba_set_intrinsics_with_affine allows it.)  A cost-only launch stores no record, so only the affine residual — another
+// residual — has a kernel of its own for it; with both switches on every on-device solve refuses, so no cost-only
+// launch is reached and none is compiled for the 26-column tag.
 template <class T>
 struct Tag { using type = T; };
 template <int M>
@@ -452,10 +461,11 @@ void dispatch_format(const pba_engine* e, int mode, F&& fn) {
   auto modes = [&](auto tag) {
     if (mode == 1) fn(tag, Mode<1>{});
     else if (mode == 0) fn(tag, Mode<0>{});
-    else if constexpr (std::is_same<decltype(tag), Tag<AffineF32>>::value) fn(tag, Mode<2>{});
+    else if constexpr (RecFormat<typename decltype(tag)::type>::kAffine) fn(Tag<AffineF32>{}, Mode<2>{});
     else fn(Tag<float>{}, Mode<2>{});
   };
-  if (e->affine) modes(Tag<AffineF32>{});
+  if (e->affine && e->opt_intr) modes(Tag<IntrAffineF32>{});
+  else if (e->affine) modes(Tag<AffineF32>{});
   else if (e->opt_intr) modes(Tag<IntrF32>{});
   else if (e->record_format == PBA_RECORD_F16_SCALED) modes(Tag<ScaledF16>{});
   else if (e->record_format == PBA_RECORD_F16) modes(Tag<_Float16>{});

@@ -1427,6 +1427,7 @@ static int gn_prepare(pba_engine* e) {
 
 int ensure_prepared(pba_engine* e, bool distributed) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
+  if (int rc = solve_refuses_both(e)) return rc;  // (the two solve switches below make no difference to it)
   if (e->n_blocks <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_blocks first");
   if (!e->state_set) return fail(PBA_ERR_NOT_READY, "pba_set_state first");
   if (e->opt.residual_kind == PBA_RESIDUAL_PHOTOMETRIC && (!e->have_images || e->P <= 0))

@@ -655,7 +655,11 @@ __device__ __forceinline__ Affine block_affine(const KernelArgs& a, int blk, int
 // AFF: the affine brightness residual r = (I − b_t) − E·(I_h − b_h) with the block's `af` (block_affine); at a = b = 0
 // both differences and the product are exact, so r is I − I_h bit for bit.  ∇I does not depend on (a, b): the
 // Jacobian chain is unchanged, and the caller forms the four brightness columns from E, I_h and b_h.
-template <int PM, bool JAC, class TB = TileBlock, bool C1 = false, bool INTR = false, bool AFF = false>
+// PFIN (the 26-column records, in both of their modes): a row whose projection is not finite is not ok.  The
+// interpolator clamps a NaN position to an in-bounds read, so a non-finite intrinsics state (fx = NaN passes the
+// pinhole domain test, which looks at p̃ alone) would otherwise leave a finite r and a valid block.
+template <int PM, bool JAC, class TB = TileBlock, bool C1 = false, bool INTR = false, bool AFF = false,
+          bool PFIN = false>
 __device__ __forceinline__ Row photometric_row(const KernelArgs& a, const TB& tb, float2 off, float Ih,
                                                const CamRec* tab = nullptr, float* ji = nullptr,
                                                const Affine* af = nullptr) {
@@ -679,6 +683,7 @@ __device__ __forceinline__ Row photometric_row(const KernelArgs& a, const TB& tb
   if (AFF) o.r = (I - af->bt) - af->E * (Ih - af->bh);
   else o.r = I - Ih;  // photometric_error.h:179
   o.ok = dom && isfinite(o.r);
+  if constexpr (PFIN) o.ok = o.ok && isfinite(u) && isfinite(v);
   if (JAC) {
     // q = ∇I · ∂π/∂p̃ (1×3)
     const Vec3 pf = to_f(p), bf = to_f(b);
@@ -1065,6 +1070,9 @@ struct pba_engine {
   bool affine = false;               // pba_set_affine_brightness: r = (I − b_t) − E·(I_h − b_h), 18-column records
   pba::detail::DevBuf<double> affine_state;  // its state [a_0 b_0 a_1 b_1 …] (2 per keyframe; zeros after pba_set_frames)
   bool gn_solve_affine = false;      // pba_gn_set_solve_affine: the on-device solve runs at that state, held constant
+  // pba_set_intrinsics_with_affine: opt_intr and affine accept each other (26-column records, evaluation only: every
+  // on-device solve refuses an engine with both on, solve_refuses_both)
+  bool intr_with_affine = false;
   pba::detail::DevBuf<float> intr_state;     // its projection constants (8 floats per camera) at the active level
   pba::detail::DevBuf<double> intr_state_d;  // and fp64 camera records (kCamD per camera)
   // photometric engines: the level-0 state as the caller set it (8 per camera); the device copy above is its image at
@@ -1091,8 +1099,9 @@ struct pba_engine {
   // the on-device Gauss-Newton solve carries the intrinsics state as unknowns (the border of the reduced system)
   bool gn_free_intr() const { return opt_intr && (opt.residual_kind == PBA_RESIDUAL_GEOMETRIC || gn_solve_intr); }
   // values per record: [r | J_host | J_target | J_rho] (14R), + J_intr (8R) with pba_set_optimize_intrinsics, or
-  // + J_ab_host | J_ab_target (2R each) with pba_set_affine_brightness (the two are not combined)
-  int rec_floats() const { return (affine ? 18 : opt_intr ? 22 : 14) * R(); }
+  // + J_ab_host | J_ab_target (2R each) with pba_set_affine_brightness; both tails, J_intr first, when
+  // pba_set_intrinsics_with_affine has let the two switches meet (26R)
+  int rec_floats() const { return (14 + (opt_intr ? 8 : 0) + (affine ? 4 : 0)) * R(); }
   // device bytes per record as stored: fp32 values, halves, or halves with the scale column (15R, pba.h)
   int rec_bytes() const {
     return record_format == PBA_RECORD_F16_SCALED ? 30 * R() : (record_format == PBA_RECORD_F16 ? 2 : 4) * rec_floats();
@@ -1104,6 +1113,16 @@ namespace detail {
 
 inline int check_device(pba_engine* e) {
   PBA_HIP(hipSetDevice(e->opt.device));
+  return PBA_OK;
+}
+
+// Free intrinsics together with affine brightness (pba_set_intrinsics_with_affine) is an evaluation format, the
+// 26-column records: no on-device solve linearises it, whatever pba_gn_set_solve_intrinsics / _affine say.  Every solve
+// entry point asks this before it prepares, plans or moves anything.
+inline int solve_refuses_both(const pba_engine* e) {
+  if (e->opt_intr && e->affine)
+    return fail(PBA_ERR_INVALID_ARGUMENT,
+                "no on-device solve with free intrinsics and affine brightness together (evaluation records only)");
   return PBA_OK;
 }
 

@@ -277,6 +277,7 @@ int pba_solve_pyramid(pba_engine* e, const pba_solver_options* options, pba_solv
   // pba_gn_set_solve_affine the levels solve at the engine's affine state, which they share
   if (e->affine && !e->gn_solve_affine)
     return fail(PBA_ERR_INVALID_ARGUMENT, "the on-device Gauss-Newton solve does not support affine brightness");
+  if (int rc = solve_refuses_both(e)) return rc;  // (with both solve switches on: still before a level is switched)
   if (e->affine && e->gn.lin_legacy)  // (the test build's A/B hook: ensure_prepared would refuse after the level switch)
     return fail(PBA_ERR_INVALID_ARGUMENT, "the 14-column lineariser has no affine brightness form");
   const int n = std::max(1, (int)e->pyr.size());

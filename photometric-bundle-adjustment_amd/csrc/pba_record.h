@@ -1,9 +1,10 @@
 // pba_record.h — the photometric record: its formats, its column layout and the staging of one pixel row.
 //
 // A block's record over its P pattern pixels is [r | J_host (P×6) | J_target (P×6) | J_ρ | tail]; the tail is the
-// format's: none (fp32, PBA_RECORD_F16), the row scales e (PBA_RECORD_F16_SCALED), J_intr (P×8, free intrinsics) or
-// J_ab_host | J_ab_target (P×2 each, affine brightness).  The block kernels (pba_evaluate.hip) stage their records in
-// LDS through the functions below; the decodes (decode_records_kernel, pba_get_records) read the layout from here too.
+// format's: none (fp32, PBA_RECORD_F16), the row scales e (PBA_RECORD_F16_SCALED), J_intr (P×8, free intrinsics),
+// J_ab_host | J_ab_target (P×2 each, affine brightness) or J_intr followed by the two brightness blocks (both).  The
+// block kernels (pba_evaluate.hip) stage their records in LDS through the functions below; the decodes
+// (decode_records_kernel, pba_get_records) read the layout from here too.
 #pragma once
 
 #include <type_traits>
@@ -19,9 +20,12 @@ namespace {
 // [r | J_host | J_target | J_rho | J_intr (P×8)].
 // Storage tag of the fp32 records with affine brightness (pba_set_affine_brightness): 18 floats per row,
 // [r | J_host | J_target | J_rho | J_ab_host (P×2) | J_ab_target (P×2)].
+// Storage tag of the fp32 records with both (pba_set_intrinsics_with_affine): 26 floats per row,
+// [r | J_host | J_target | J_rho | J_intr (P×8) | J_ab_host (P×2) | J_ab_target (P×2)].
 struct ScaledF16 {};
 struct IntrF32 {};
 struct AffineF32 {};
+struct IntrAffineF32 {};
 template <class Stored, int Cols, bool Scaled = false, bool Intr = false, bool Affine = false>
 struct RecLayout {
   using S = Stored;
@@ -36,6 +40,8 @@ template <>
 struct RecFormat<IntrF32> : RecLayout<float, 22, false, true> {};
 template <>
 struct RecFormat<AffineF32> : RecLayout<float, 18, false, false, true> {};
+template <>
+struct RecFormat<IntrAffineF32> : RecLayout<float, 26, false, true, true> {};
 
 }  // namespace
 
@@ -50,9 +56,18 @@ __host__ __device__ __forceinline__ constexpr int col_jhost(int P) { return P; }
 __host__ __device__ __forceinline__ constexpr int col_jtarget(int P) { return 7 * P; }
 __host__ __device__ __forceinline__ constexpr int col_jrho(int P) { return 13 * P; }
 __host__ __device__ __forceinline__ constexpr int col_tail(int P) { return 14 * P; }
-// the affine tail: J_ab_host (P×2), then J_ab_target (P×2)
-__host__ __device__ __forceinline__ constexpr int col_jab_host(int P) { return col_tail(P); }
-__host__ __device__ __forceinline__ constexpr int col_jab_target(int P) { return col_tail(P) + 2 * P; }
+// the affine tail: J_ab_host (P×2), then J_ab_target (P×2); INTR (the format's kIntr): behind J_intr (P×8 from
+// col_tail) in the format that has both — columns 14·P and 16·P of the 18-column record, 22·P and 24·P of the 26-column one
+template <bool INTR = false>
+__host__ __device__ __forceinline__ constexpr int col_jab_host(int P) {
+  if constexpr (INTR) return col_tail(P) + 8 * P;
+  else return col_tail(P);
+}
+template <bool INTR = false>
+__host__ __device__ __forceinline__ constexpr int col_jab_target(int P) {
+  if constexpr (INTR) return col_tail(P) + 10 * P;
+  else return col_tail(P) + 2 * P;
+}
 
 // The pixel row whose scale e applies to column c of the decoded record (PBA_RECORD_F16_SCALED: a Jacobian entry of
 // pixel row k is stored divided by e[k], at col_tail + k); −1 for the residual columns, which are not scaled.
@@ -74,14 +89,18 @@ __device__ __forceinline__ _Float16 rec_val<_Float16>(float v) {
 // Row px of J_ab_host = [E·(I_h − b_h), E] and J_ab_target = [−E·(I_h − b_h), −1] (2 floats each at col_jab_host + 2·px
 // and col_jab_target + 2·px of the block's staged record), g = E·(I_h − b_h): two 8-B LDS writes.  A block's record is
 // 72·P bytes and the rows start 56·P + 8·px and 64·P + 8·px into it: 8-B aligned at every P, odd ones included.
+// INTR (the format's kIntr): the rows sit behind J_intr — a 104·P-byte record, the rows 88·P + 8·px and 96·P + 8·px into
+// it, 8-B aligned at every P as well.
 // ok = false: the zero rows of an invalid block.
+template <bool INTR = false>
 __device__ __forceinline__ void stage_affine(float* s_rec, int P, int px, float g, float E, bool ok) {
-  reinterpret_cast<float2*>(s_rec + col_jab_host(P))[px] = ok ? make_float2(g, E) : make_float2(0.0f, 0.0f);
-  reinterpret_cast<float2*>(s_rec + col_jab_target(P))[px] = ok ? make_float2(-g, -1.0f) : make_float2(0.0f, 0.0f);
+  reinterpret_cast<float2*>(s_rec + col_jab_host<INTR>(P))[px] = ok ? make_float2(g, E) : make_float2(0.0f, 0.0f);
+  reinterpret_cast<float2*>(s_rec + col_jab_target<INTR>(P))[px] = ok ? make_float2(-g, -1.0f) : make_float2(0.0f, 0.0f);
 }
 
 // Row px of J_intr (8 floats at col_tail + 8·px of the block's staged record): two 16-B LDS writes when the row is 16-B
-// aligned — a block's record is 88·P bytes and the row starts 56·P + 32·px into it, so for even P — else four 8-B ones.
+// aligned — a block's record is 88·P bytes (104·P with the brightness blocks behind it: a multiple of 16 for the same P)
+// and the row starts 56·P + 32·px into it, so for even P — else four 8-B ones.
 __device__ __forceinline__ void stage_intr(float* s_rec, int P, int px, const float (&ji)[8]) {
   float* d = s_rec + col_tail(P) + 8 * px;
   if ((P & 1) == 0) {

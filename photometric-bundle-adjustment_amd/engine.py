@@ -192,6 +192,7 @@ def lib(path: Optional[str] = None):
         "pba_set_intrinsics_state": ([vp, vp], C.c_int),
         "pba_get_intrinsics": ([vp, vp], C.c_int),
         "pba_set_affine_brightness": ([vp, i32], C.c_int),
+        "pba_set_intrinsics_with_affine": ([vp, i32], C.c_int),
         "pba_set_affine_state": ([vp, vp], C.c_int),
         "pba_set_affine_state_device": ([vp, vp], C.c_int),
         "pba_get_affine_state": ([vp, vp], C.c_int),
@@ -397,13 +398,14 @@ class Engine:
     @property
     def record_floats(self) -> int:
         """Values per record as records() returns them (pba_record_floats): 14·R in every record format, 22·R with
-        set_optimize_intrinsics, 18·R with set_affine_brightness (fp32 records only)."""
+        set_optimize_intrinsics, 18·R with set_affine_brightness, 26·R with both (set_intrinsics_with_affine); the last
+        three are fp32 records only."""
         return self._L.pba_record_floats(self._h)
 
     @property
     def record_bytes(self) -> int:
-        """Device bytes per record as stored (pba_record_bytes): 4·record_floats (56·R, or 88·R with free intrinsics),
-        28·R or 30·R by format."""
+        """Device bytes per record as stored (pba_record_bytes): 4·record_floats (56·R, 88·R with free intrinsics, 72·R
+        with affine brightness, 104·R with both), 28·R or 30·R by format."""
         return self._L.pba_record_bytes(self._h)
 
     def records_raw(self) -> np.ndarray:
@@ -623,10 +625,18 @@ class Engine:
     def set_affine_brightness(self, enable: bool = True):
         """r_k = (I_t − b_t) − exp(a_t − a_h)·(I_h,k − b_h) with the affine state (set_affine_state; zeros when enabled
         and after every set_problem); the records grow to 18·R values with J_ab_host and J_ab_target (R×2 each) as their
-        tail (split_record).  fp32 records only; not combined with set_optimize_intrinsics; the on-device solve refuses
-        unless gn_set_solve_affine opts in."""
+        tail (split_record).  fp32 records only; combined with set_optimize_intrinsics only after
+        set_intrinsics_with_affine; the on-device solve refuses unless gn_set_solve_affine opts in."""
         self._ck(self._L.pba_set_affine_brightness(self._h, int(bool(enable))), "pba_set_affine_brightness")
         self.record = self._L.pba_record_floats(self._h)
+
+    def set_intrinsics_with_affine(self, enable: bool = True):
+        """Let set_optimize_intrinsics and set_affine_brightness accept each other, in either order (off by default: they
+        refuse each other).  With both on the records are 26·R values, [r | J_host | J_target | J_rho | J_intr (R×8) |
+        J_ab_host (R×2) | J_ab_target (R×2)] (split_record gives the seven parts), and every on-device solve refuses:
+        the records are for an outer solver.  The switch alone changes no record.  Refused on a geometric engine, with a
+        half record format active, and when turned off while both switches are on."""
+        self._ck(self._L.pba_set_intrinsics_with_affine(self._h, int(bool(enable))), "pba_set_intrinsics_with_affine")
 
     def gn_set_solve_affine(self, enable: bool = True):
         """Photometric engines with set_affine_brightness: the single-GPU on-device Gauss-Newton (gn_linearize / gn_step /
@@ -939,11 +949,15 @@ def outlier_landmarks(n_points: int, obs_point, obs_frame, flags, obs_is_outlier
 def split_record(rec: np.ndarray, R: int):
     """(r, J_host, J_target, J_rho) views of a record array — and J_intr (n, R, 8) as a fifth when the records carry it
     (22·R values per record: set_optimize_intrinsics), or J_ab_host and J_ab_target (n, R, 2 each) as a fifth and sixth
-    (18·R values per record: set_affine_brightness)."""
+    (18·R values per record: set_affine_brightness), or all three, J_intr first, as a fifth to seventh (26·R values per
+    record: both, set_intrinsics_with_affine)."""
     n = rec.shape[0]
     parts = (rec[:, :R], rec[:, R:7 * R].reshape(n, R, 6), rec[:, 7 * R:13 * R].reshape(n, R, 6), rec[:, 13 * R:14 * R])
     if rec.shape[1] == 22 * R:
         parts += (rec[:, 14 * R:22 * R].reshape(n, R, 8),)
     elif rec.shape[1] == 18 * R:
         parts += (rec[:, 14 * R:16 * R].reshape(n, R, 2), rec[:, 16 * R:18 * R].reshape(n, R, 2))
+    elif rec.shape[1] == 26 * R:
+        parts += (rec[:, 14 * R:22 * R].reshape(n, R, 8), rec[:, 22 * R:24 * R].reshape(n, R, 2),
+                  rec[:, 24 * R:26 * R].reshape(n, R, 2))
     return parts
