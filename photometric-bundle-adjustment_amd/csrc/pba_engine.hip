@@ -675,8 +675,23 @@ int evaluate_at(pba_engine* e, const double* poses, const double* rho, bool adop
       rho = e->rho.p;
       adopt = false;
     }
-    ka = make_kernel_args(e, nullptr, rho);
-    ka.poses = poses;
+    if (test_hook("PBA_TEST_PAIR_TABLE")) {
+      // test build: the block kernels' pair-table prologue (stage_tile, a.poses == nullptr), which no launch of a
+      // photometric engine takes otherwise — every evaluation and every cost-only launch is at a fused state.  The
+      // state is copied first, the table formed from it, and the launch reads the table.
+      if (adopt) {
+        if (int rc = pba_set_state_device(e, poses, rho)) return rc;
+        poses = e->poses.p;
+        rho = e->rho.p;
+        adopt = false;
+      }
+      launch_pairs(e, poses, e->pairs.p);
+      e->pairs_fresh = false;
+      ka = make_kernel_args(e, e->pairs.p, rho);
+    } else {
+      ka = make_kernel_args(e, nullptr, rho);
+      ka.poses = poses;
+    }
     if (adopt) {
       PBA_HIP(e->poses.resize(7 * (size_t)e->n_frames));
       ka.adopt_poses = e->poses.p;

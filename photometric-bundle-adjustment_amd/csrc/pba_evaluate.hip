@@ -25,6 +25,28 @@ using namespace pba::detail;
 
 namespace {
 
+// PBA_EVAL_STAMPS (a variant built with tools/build_variant.sh, never the product or the test library): wave 0 of every
+// workgroup of the 8-lane record kernel takes 100-MHz stamps along its chain of loads and barriers — kept in scalar
+// registers and stored behind the slab, so that a stamp's store is not in the vector-memory counter a later stamp
+// waits for.  "Arrived" stamps wait for every outstanding load first, which the unstamped kernel does only where it
+// needs a value: the stamped variant times the chain's links, not the product kernel.  tools/probe/block_chain_stamps.py.
+#ifdef PBA_EVAL_STAMPS
+// entry | block_rec | prologue loads | barrier 1 | I_h | row | stage may begin | staged | stored
+constexpr int kEvalStamps = 9;
+__device__ long long* g_eval_stamps = nullptr;  // 16 per workgroup, at blockIdx.x
+#define PBA_STAMP(i, wait_loads)                                        \
+  do {                                                                  \
+    if (wait_loads) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    \
+    __builtin_amdgcn_sched_barrier(0);                                  \
+    stamps[i] = wall_clock64();                                         \
+    __builtin_amdgcn_sched_barrier(0);                                  \
+  } while (0)
+#else
+#define PBA_STAMP(i, wait_loads) \
+  do {                           \
+  } while (0)
+#endif
+
 // PM = camera model + 4 · interpolator; T = float, _Float16, ScaledF16, IntrF32, AffineF32 or IntrAffineF32 (RecFormat;
 // the last stages 32·26·8·4 = 26,624 B)
 template <int PM, int LPB, int MODE, class T>
@@ -33,44 +55,80 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
   constexpr bool JAC = MODE == 1;
   using S = typename RecFormat<T>::S;  // the stored type
   constexpr int kCols = RecFormat<T>::kCols;
-  constexpr int kStageBytes = JAC ? BPW * kCols * LPB * (int)sizeof(S) : 0;
-  constexpr int kTileBytes = BPW * (int)sizeof(TileBlock);
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kStageBytes > kTileBytes ? kStageBytes : kTileBytes];
-  TileBlock* s_tb = reinterpret_cast<TileBlock*>(lds);
+  // one LDS region per wave: its 8 tile blocks, then over the same bytes its 8 staged records (pba_wave_slab.h)
+  static_assert(LPB == kSlabMaxPattern && BPW == kSlabWaves * kSlabWaveBlocks && sizeof(TileBlock) == kSlabTileBytes,
+                "pba_wave_slab.h: 4 waves of 8 blocks, 8 lanes each");
+  static_assert(slab_format_known(kCols, (int)sizeof(S)), "pba_wave_slab.h: kSlabFormats has no entry for this format");
+  constexpr int kRegion = wave_region_bytes(kCols, (int)sizeof(S), JAC);
+  __shared__ __attribute__((aligned(16))) unsigned char lds[wg_lds_bytes(kCols, (int)sizeof(S), JAC)];
+  auto tile_at = [&](int b) { return reinterpret_cast<TileBlock*>(lds + tile_block_offset(b, kRegion)); };
+  // the wave's own region from a scalar register (the wave index is uniform): a lane's tile block and staged record
+  // then hang off one per-lane value, its block's index in the wave, as they hung off lb before the regions
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+  unsigned char* const region = lds + wave_region_offset(w, kRegion);
   const int P = a.P;
   const int rec_f = kCols * P;
   const int blk0 = logical_tile() * BPW;
-  const int lb = threadIdx.x / LPB;
+  const int wb = (threadIdx.x / LPB) % kSlabWaveBlocks;  // the block's index in its wave
+  const int lb = w * kSlabWaveBlocks + wb;               // and in the tile
   const int k = threadIdx.x % LPB;
   const int blk = blk0 + lb;
   const bool live = blk < a.n_blocks;  // a block's LPB lanes agree
   const bool act = live && k < P;
+  TileBlock* const own_tile = reinterpret_cast<TileBlock*>(region + wb * kSlabTileBytes);  // = tile_at(lb)
   S* out = reinterpret_cast<S*>(a.out);  // records in the engine's format (fp32, or halves: PBA_RECORD_F16 / _SCALED)
 
+#ifdef PBA_EVAL_STAMPS
+  long long stamps[kEvalStamps] = {};
+#endif
+  PBA_STAMP(0, false);
   const float2 off = pattern_at<LPB>(a, k);
   adopt_state(a);
   int pt;
+  float Ih;
+  auto host_intensity = [&]() { return act ? a.host_int[(long long)pt * P + k] : 0.0f; };
   if (LPB == 8 && a.poses) {  // fused state: the workgroup-cooperative prologue (BPW = 32)
     static_assert(kBlockThreads == 256, "stage_tile_wg: 4 waves, 32 blocks");
-    pt = a.block_rec[live ? blk : a.n_blocks - 1].x;
-    stage_tile_wg(a, s_tb, blk0);
+    // lane b (and b + 32) of every wave loads tile block b's record for the prologue: the lane's own point comes
+    // from it by a lane move, not from a second load.  I_h needs only the point: issued before the prologue's loads,
+    // it is in flight with them (a cold line, like u_ref) and the prologue's own wait covers it — the vector-memory
+    // counter retires in order
+    const int4 br = tile_block_rec(a, blk0);
+#ifdef PBA_EVAL_STAMPS
+    asm volatile("" ::"v"(br.x));
+    PBA_STAMP(1, true);
+#endif
+    pt = __shfl(br.x, lb, 64);
+    Ih = host_intensity();
+    stage_tile_wg(a, tile_at, br);
   } else {
-    pt = stage_tile<LPB>(a, s_tb, lb, k, blk, live);
+    pt = stage_tile<LPB>(a, own_tile, 0, k, blk, live);
+    Ih = host_intensity();
   }
-  const float Ih = act ? a.host_int[(long long)pt * P + k] : 0.0f;
   constexpr bool AFF = RecFormat<T>::kAffine;
   Affine af = {1.0f, 0.0f, 0.0f};
   if constexpr (AFF) af = block_affine(a, live ? blk : a.n_blocks - 1);
+  PBA_STAMP(2, true);
   __syncthreads();
+  PBA_STAMP(3, false);
+#ifdef PBA_EVAL_STAMPS
+  asm volatile("" ::"v"(Ih));
+  PBA_STAMP(4, true);
+#endif
   constexpr bool INTR = JAC && RecFormat<T>::kIntr;
   constexpr bool PFIN = RecFormat<T>::kIntr && AFF;  // the 26-column records: a non-finite projection is invalid
   float ji[8];
   // dead lanes evaluate a staged block, masked by act
-  const Row row = photometric_row<PM, JAC, TileBlock, false, INTR, AFF, PFIN>(a, s_tb[lb], off, Ih, nullptr, ji, &af);
+  const Row row =
+      photometric_row<PM, JAC, TileBlock, false, INTR, AFF, PFIN>(a, *own_tile, off, Ih, nullptr, ji, &af);
   // per-block validity (ballot over the wave: the block's LPB lanes are an aligned bit field) and ‖r‖²
   const int ok = group_all<LPB>(act ? row.ok : 1);
   const float s = group_sum<LPB>(act ? row.r * row.r : 0.0f);
   const float bc = ok ? huber_cost(s, a.huber) : 0.0f;
+#ifdef PBA_EVAL_STAMPS
+  asm volatile("" ::"v"(bc));
+  PBA_STAMP(5, false);
+#endif
   if (live && k == 0) {
     a.valid[blk] = (uint8_t)ok;
     a.cost[blk] = bc;
@@ -89,10 +147,14 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
     }
     return;
   }
-  __syncthreads();  // every lane has read its tile block: the record stage may overwrite it
+  // the record stage overwrites the wave's own tile blocks, which only its lanes read (one wave's LDS operations
+  // stay in order): no barrier.  The tile was read as TileBlock, the stage is written as S: the compiler must not
+  // move the stores above the reads
+  asm volatile("" ::: "memory");
+  PBA_STAMP(6, false);
   // stage the record row of pixel k (pba_record.h), zeros for invalid blocks.  The form of these stores is pinned: the
   // rows' fp32 arithmetic contracts differently around other stores, which changes record bytes
-  S* s_rec = reinterpret_cast<S*>(lds) + lb * rec_f;
+  S* s_rec = reinterpret_cast<S*>(region + wb * rec_f * (int)sizeof(S));  // lds + staged_record_offset(lb, …)
   if constexpr (RecFormat<T>::kScaled) {
     stage_row_scaled(s_rec, lb, P, k, row, act && ok);
     if (act && !ok) {
@@ -118,11 +180,20 @@ __global__ __launch_bounds__(kBlockThreads) void photometric_block_kernel(const 
     }
     if constexpr (AFF) stage_affine<RecFormat<T>::kIntr>(s_rec, P, k, af.E * (Ih - af.bh), af.E, ok != 0);
   }
-  __syncthreads();
+  // each wave stores its own run of records (contiguous in LDS and in the record array) once its lanes have staged
+  // them: no barrier, a wave does not wait for another wave's taps
+  asm volatile("" ::: "memory");
+  PBA_STAMP(7, false);
   const int nblk = min(BPW, a.n_blocks - blk0);
   if (nblk <= 0) return;
-  store_slab<S>(lds, reinterpret_cast<unsigned char*>(out + (long long)blk0 * rec_f), nblk * rec_f * (int)sizeof(S),
-                a.slab_wt);
+  const WaveStore ws = wave_store_range(w, nblk, rec_f * (int)sizeof(S));
+  store_slab<S, 64>(region, reinterpret_cast<unsigned char*>(out + (long long)blk0 * rec_f) + ws.begin,
+                    ws.bytes, a.slab_wt, threadIdx.x % 64);
+#ifdef PBA_EVAL_STAMPS
+  PBA_STAMP(8, true);
+  if (threadIdx.x == 0 && g_eval_stamps)
+    for (int i = 0; i < kEvalStamps; ++i) g_eval_stamps[16LL * blockIdx.x + i] = stamps[i];
+#endif
 }
 
 // Patterns of 9…32 pixels (the 21-px pattern of config C5): still 8 lanes per block, each lane evaluating pixels
@@ -516,6 +587,13 @@ void launch_photometric(pba_engine* e, const KernelArgs& ka, int mode) {
 }
 
 }  // namespace
+
+#ifdef PBA_EVAL_STAMPS
+// test-only entry of the stamped variant: 16 int64 per workgroup of the next 8-lane record launches (nullptr: none)
+extern "C" int pba_test_set_eval_stamps(long long* d_stamps) {
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_eval_stamps), &d_stamps, sizeof(d_stamps)) == hipSuccess ? 0 : -1;
+}
+#endif
 
 namespace pba {
 namespace detail {

@@ -482,11 +482,18 @@ __device__ __forceinline__ int stage_tile_pp(const KernelArgs& a, TileBlock* s_t
 // with its fp32 copy), wave 3 the point data (lanes 0-31 u_ref, 32-63 ρ).  The fp64 relative-pose arithmetic is then
 // issued once per workgroup instead of once per wave (SIMT: a wave pays for every branch any of its lanes takes, so
 // the rotation and translation branches of stage_tile cost each of the four waves both).  The caller barriers.
-__device__ __forceinline__ void stage_tile_wg(const KernelArgs& a, TileBlock* s_tb, int blk0) {
+// br: the lane's block record (tile_block_rec); tile_at(b): where tile block b goes (the 8-lane kernel keeps one LDS
+// region per wave, pba_wave_slab.h).
+__device__ __forceinline__ int4 tile_block_rec(const KernelArgs& a, int blk0) {
+  const int b = threadIdx.x & 31;
+  return a.block_rec[min(blk0 + b, a.n_blocks - 1)];  // a dead block stages the last block
+}
+template <class Place>
+__device__ __forceinline__ void stage_tile_wg(const KernelArgs& a, Place tile_at, const int4 br) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, b = lane & 31;
-  const int4 br = a.block_rec[min(blk0 + b, a.n_blocks - 1)];  // a dead block stages the last block
-  PairRec& pr = s_tb[b].pr;
-  uint4* dst = reinterpret_cast<uint4*>(s_tb + b);
+  TileBlock* const tb = tile_at(b);
+  PairRec& pr = tb->pr;
+  uint4* dst = reinterpret_cast<uint4*>(tb);
   if (w == 0) {
     if (lane < 32) {
       const double* H = a.poses + 7 * br.y;
@@ -537,6 +544,10 @@ __device__ __forceinline__ void stage_tile_wg(const KernelArgs& a, TileBlock* s_
       dst[kPairParts + 1] = make_uint4(__double2loint(rho), __double2hiint(rho), (unsigned)img, (unsigned)(img >> 32));
     }
   }
+}
+
+__device__ __forceinline__ void stage_tile_wg(const KernelArgs& a, TileBlock* s_tb, int blk0) {
+  stage_tile_wg(a, [=](int b) { return s_tb + b; }, tile_block_rec(a, blk0));
 }
 
 // The same for the compact tile (TileBlockC) and the LDS camera table of n_cams ≤ kCamTab cameras: waves 0, 1 and 3
@@ -596,14 +607,27 @@ __device__ __forceinline__ void stage_tile_wg_ct(const KernelArgs& a, TileBlockC
 
 // Pattern offset k (k < N) read from the kernel arguments with scalar loads at constant offsets and picked per lane
 // by selects.  A lane-indexed read of the argument block is a vector-memory load, and staging it through LDS made
-// every workgroup wait one memory round trip before it issued any other load.
+// every workgroup wait one memory round trip before it issued any other load.  Each offset is pinned in a scalar
+// register before its select: left alone the compiler turns the selects of values into selects of addresses and
+// reads the argument block with per-lane vector loads after all, which the in-order vector-memory
+// counter then makes every later wait of the prologue cover.
 template <int N>
 __device__ __forceinline__ float2 pattern_at(const KernelArgs& a, int k) {
-  float2 o = make_float2(a.pattern[0], a.pattern[1]);
+  typedef float pat2 __attribute__((ext_vector_type(2)));
+  auto pinned = [&](int j) {
+    pat2 v = {a.pattern[2 * j], a.pattern[2 * j + 1]};
+    asm("" : "+s"(v));
+    return v;
+  };
+  // (the pair stays one 2-vector to the end, as the vector load's result was: the rows' packed fp32 arithmetic is
+  // formed from it, and from two separate floats the compiler packs and contracts the rows differently)
+  pat2 o = pinned(0);
 #pragma unroll
-  for (int j = 1; j < N; ++j)
-    if (k == j) o = make_float2(a.pattern[2 * j], a.pattern[2 * j + 1]);
-  return o;
+  for (int j = 1; j < N; ++j) {
+    const pat2 p = pinned(j);
+    o = k == j ? p : o;
+  }
+  return make_float2(o.x, o.y);
 }
 
 // The launch that evaluates at a caller's state also adopts it: one element per lane (grid ≥ frames·7, points).

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "pba_internal.h"
+#include "pba_wave_slab.h"
 
 // The storage tags sit in an unnamed namespace like the kernels they parameterise (a kernel's name carries its tag).
 namespace {
@@ -42,6 +43,16 @@ template <>
 struct RecFormat<AffineF32> : RecLayout<float, 18, false, false, true> {};
 template <>
 struct RecFormat<IntrAffineF32> : RecLayout<float, 26, false, true, true> {};
+
+// every format's entry in the table the host check of the per-wave stores walks (pba_wave_slab.h)
+template <class T>
+constexpr bool slab_entry_is(int i) {
+  return pba::detail::kSlabFormats[i].cols == RecFormat<T>::kCols &&
+         pba::detail::kSlabFormats[i].ssize == (int)sizeof(typename RecFormat<T>::S);
+}
+static_assert(slab_entry_is<float>(0) && slab_entry_is<_Float16>(1) && slab_entry_is<ScaledF16>(2) &&
+                  slab_entry_is<IntrF32>(3) && slab_entry_is<AffineF32>(4) && slab_entry_is<IntrAffineF32>(5),
+              "pba_wave_slab.h: kSlabFormats");
 
 }  // namespace
 
@@ -117,30 +128,33 @@ __device__ __forceinline__ void stage_intr(float* s_rec, int P, int px, const fl
 // wt (wave-uniform, KernelArgs::slab_wt): non-temporal write-through stores (`nt sc1`) — for launches of at most one
 // wave of workgroups (a 1/8 shard of C4: 8.29 → 8.07-8.15 µs, nothing left dirty in L2 for the kernel's end), never for
 // a full C4 launch (44.9 → 46.2 µs), DESIGN.md §3.
+// NTH threads share the slab, thread tid of them calling: the workgroup (the default), or one wave storing its own
+// run of records (NTH = 64, tid = its lane: photometric_block_kernel, pba_wave_slab.h).
 template <class T, int NTH = kBlockThreads>
-__device__ __forceinline__ void store_slab(const unsigned char* src, unsigned char* dst, int bytes, int wt = 0) {
-  constexpr int kBlockThreads = NTH;  // the workgroup's threads share the slab
+__device__ __forceinline__ void store_slab(const unsigned char* src, unsigned char* dst, int bytes, int wt = 0,
+                                           int tid = threadIdx.x) {
+  constexpr int kBlockThreads = NTH;
   if ((((uintptr_t)dst | (unsigned)bytes) & 15) == 0) {
     // non-temporal 16-B stores (write-through sc1 stores measured 49 → 71 µs for this kernel; per-lane stores
     // straight from registers, without the LDS slab, 49 → 104 µs: DESIGN.md §3)
     const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
     f32x4* d4 = reinterpret_cast<f32x4*>(dst);
     if (wt) {
-      for (int i = threadIdx.x; i < (bytes >> 4); i += kBlockThreads)
+      for (int i = tid; i < (bytes >> 4); i += kBlockThreads)
         asm volatile("global_store_dwordx4 %0, %1, off nt sc1" ::"v"(d4 + i), "v"(s4[i]) : "memory");
     } else {
-      for (int i = threadIdx.x; i < (bytes >> 4); i += kBlockThreads) __builtin_nontemporal_store(s4[i], d4 + i);
+      for (int i = tid; i < (bytes >> 4); i += kBlockThreads) __builtin_nontemporal_store(s4[i], d4 + i);
     }
   } else if (sizeof(T) == 4 || (((uintptr_t)dst | (unsigned)bytes) & 3) == 0) {
     const float* s1 = reinterpret_cast<const float*>(src);
     float* d1 = reinterpret_cast<float*>(dst);
 #pragma unroll 1
-    for (int i = threadIdx.x; i < (bytes >> 2); i += kBlockThreads) __builtin_nontemporal_store(s1[i], d1 + i);
+    for (int i = tid; i < (bytes >> 2); i += kBlockThreads) __builtin_nontemporal_store(s1[i], d1 + i);
   } else {
     const _Float16* s1 = reinterpret_cast<const _Float16*>(src);
     _Float16* d1 = reinterpret_cast<_Float16*>(dst);
 #pragma unroll 1
-    for (int i = threadIdx.x; i < (bytes >> 1); i += kBlockThreads) d1[i] = s1[i];
+    for (int i = tid; i < (bytes >> 1); i += kBlockThreads) d1[i] = s1[i];
   }
 }
 
