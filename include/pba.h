@@ -252,7 +252,12 @@ int pba_get_affine_state(pba_engine* engine, double* ab);
  * With both on, every on-device solve entry point returns PBA_ERR_INVALID_ARGUMENT and changes nothing, whatever
  * pba_gn_set_solve_intrinsics and pba_gn_set_solve_affine say: pba_gn_*, pba_solve, pba_solve_pyramid,
  * pba_gn_step_export/import, pba_solve_distributed(_comm), pba_affine_*, pba_solve_affine, pba_joint_*,
- * pba_solve_joint, pba_joint_step_export/import and pba_solve_joint_distributed.
+ * pba_solve_joint, pba_joint_step_export/import and pba_solve_joint_distributed.  One solve runs the full problem:
+ * under pba_joint_set_solve_intrinsics (below) pba_joint_linearize / step / get_reduced_system / get_step /
+ * get_intrinsics_step / candidate_cost / accept and pba_solve_joint free the intrinsics too.  With or without that
+ * switch the rest keeps refusing: pba_joint_band / exchange_size / step_export / step_import,
+ * pba_solve_joint_distributed, pba_gn_*, pba_solve, pba_solve_pyramid, the multi-GPU Gauss-Newton, pba_affine_* and
+ * pba_solve_affine.
  * PBA_ERR_INVALID_ARGUMENT, the engine left as it was: on a geometric engine; for enable = 1 with a half record format
  * active; for enable = 0 while both switches are on (turn one off first). */
 int pba_set_intrinsics_with_affine(pba_engine* engine, int32_t enable);
@@ -321,15 +326,43 @@ int pba_affine_accept(pba_engine* engine);
  * pba_joint_accept, pba_affine_accept and pba_gn_accept (pba_solve, pba_solve_affine) leave a joint linearisation stale:
  * step, candidate cost, accept and the getters then return PBA_ERR_NOT_READY until pba_joint_linearize.
  * PBA_ERR_INVALID_ARGUMENT, nothing changed, on a geometric engine or without pba_set_affine_brightness (so never with
- * half records or free intrinsics, which affine brightness refuses); PBA_ERR_NOT_READY for a call before the one it
+ * half records), and with free intrinsics unless pba_joint_set_solve_intrinsics, below, lets the solve free them too;
+ * PBA_ERR_NOT_READY for a call before the one it
  * follows (step before linearize; candidate cost, accept and the getters before a step that succeeded). */
 int pba_joint_linearize(pba_engine* engine, double* cost);  /* cost may be NULL */
-int pba_joint_system_size(pba_engine* engine, int32_t* n);  /* 8·n_frames */
+int pba_joint_system_size(pba_engine* engine, int32_t* n);  /* 8·n_frames (+ 8·n_cams: pba_joint_set_solve_intrinsics) */
 int pba_joint_step(pba_engine* engine, double lambda, double* model_decrease, int32_t* solver_status);
 int pba_joint_get_reduced_system(pba_engine* engine, double* S_dense, double* g);
 int pba_joint_get_step(pba_engine* engine, double* d_keyframes, double* d_inv_dist);
 int pba_joint_candidate_cost(pba_engine* engine, double* cost);
 int pba_joint_accept(pba_engine* engine);
+/* The joint solve with free intrinsics: the full photometric problem — poses, inverse distances, (a, b) and the target
+ * cameras' intrinsics (BundleAdjustmentOptions::optimize_intrinsics, map_utils.h:339-345) — in one solve.  Photometric
+ * engines with both pba_set_optimize_intrinsics and pba_set_affine_brightness on (pba_set_intrinsics_with_affine).
+ * Default 0: pba_joint_* and pba_solve_joint refuse such an engine as before.  With enable = 1 they run with the rows
+ * of the 26·P record: unknowns 8 per keyframe [δpose | δa δb], then 8 per camera δk — with respect to the level-0
+ * intrinsics state, a plain parameter block, k + δk — then one δρ per point.  The rules are the joint solve's
+ * throughout: the Corrector weight in the linearisation's own float arithmetic, the damping
+ * (H + λ·clamp(diag H, 1e-6, 1e32)) δ = −g over the intrinsics too (a parameter the camera model does not use has a
+ * zero row and column, the pivot λ·1e-6, a zero gradient and a zero step), the model decrease over all free unknowns,
+ * the candidate T·exp(δ), ρ + δρ, (a, b) + δ, k + δk.  A block whose projection with the intrinsics state is not finite
+ * is invalid, as in the 26·P evaluation.
+ * pba_joint_system_size becomes 8·(n_frames + n_cams), keyframes first; pba_joint_get_reduced_system is dense at that
+ * size; pba_joint_get_step keeps its two arguments and their sizes, and pba_joint_get_intrinsics_step returns the
+ * cameras' 8·n_cams (PBA_ERR_INVALID_ARGUMENT without the switch, PBA_ERR_NOT_READY as pba_joint_get_step).
+ * Constants: a camera that no valid block targets gets identity rows, a zero gradient and a zero step; the keyframes'
+ * two halves as above, and at least one keyframe's (a, b) must be constant as above.
+ * pba_joint_accept also moves the intrinsics state to the candidate: pba_get_intrinsics then returns the solved level-0
+ * state, as after every pba_solve_joint that accepted a step.  pba_set_intrinsics_state leaves a joint linearisation
+ * stale, like pba_set_affine_state.  At pyramid level l the solve works on that level: J_intr's columns 0–3 carry 2^−l
+ * and the level's image of the state moves by 2^−l·δk in entries 0–3 and by δk in the distortion.
+ * pba_solve_joint: the step norm, the state norm and the gradient max norm include the intrinsics of the cameras that
+ * have a valid block (of the level-0 state; all 8 entries).
+ * The switch is not one of the two pba_gn_set_solve_* opt-ins, which make no difference to it.
+ * PBA_ERR_INVALID_ARGUMENT, nothing changed: enable = 1 on a geometric engine, or unless both
+ * pba_set_optimize_intrinsics and pba_set_affine_brightness are on; turning either of them off clears the switch. */
+int pba_joint_set_solve_intrinsics(pba_engine* engine, int32_t enable);
+int pba_joint_get_intrinsics_step(pba_engine* engine, double* d_intrinsics);  /* 8·n_cams */
 /* Image interpolator of the photometric residual (and of the device-sampled I_h,k): PBA_INTERP_BILINEAR (default,
  * the north star's) or PBA_INTERP_BICUBIC — Ceres' BiCubicInterpolator over Grid2D<uint8_t, 1>
  * (cubic_interpolation.h:252-344, edge clamp :403-414), the interpolator of PhotometricError<8>

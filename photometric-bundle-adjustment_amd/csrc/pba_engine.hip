@@ -249,6 +249,7 @@ int upload_intrinsics_state(pba_engine* e) {
       double* r = k.data() + 8 * (size_t)c;
       r[0] *= s; r[1] *= s; r[2] = (r[2] + 0.5) * s - 0.5; r[3] = (r[3] + 0.5) * s - 0.5;
     }
+  e->joint.linearized = false;  // (a joint linearisation with free intrinsics was formed at the old state)
   return upload_cameras(e, e->n_cams, k.data(), e->intr_state, e->intr_state_d);
 }
 
@@ -291,6 +292,8 @@ int pba_set_optimize_intrinsics(pba_engine* e, int32_t enable) {
     if (int rc = upload_intrinsics_state(e)) return rc;
   }
   e->opt_intr = on;
+  if (!on) e->joint_solve_intr = false;  // (pba_joint_set_solve_intrinsics needs both switches: asked for again)
+  e->joint.linearized = false;           // (the joint solve's unknowns and rows change with the switch)
   e->evaluated = false;
   e->res_fresh = false;
   e->pairs_fresh = false;  // (a photometric pair's target part is the state's)
@@ -323,6 +326,7 @@ int pba_set_affine_brightness(pba_engine* e, int32_t enable) {
     if (int rc = zero_affine_state(e)) return rc;
   e->affine = on;
   if (!on) e->gn_solve_affine = false;  // (the switch belongs to the affine engine: asked for again when it comes back)
+  if (!on) e->joint_solve_intr = false;
   e->evaluated = false;
   e->res_fresh = false;
   if (e->n_blocks > 0) PBA_HIP(e->out.resize((size_t)e->n_blocks * e->rec_floats()));

@@ -512,7 +512,7 @@ void launch_geometric(pba_engine* e, const KernelArgs& ka, int mode) {
 // The record format T and the compile-time mode M (1 records, 0 residuals, 2 costs only) of a photometric launch, from
 // the engine's state: calls fn(Tag<T>, Mode<M>).  The first row that holds:
 //   engine state                                    modes 1 and 0   mode 2
-//   affine brightness and free intrinsics           IntrAffineF32   AffineF32
+//   affine brightness and free intrinsics           IntrAffineF32   IntrAffineF32
 //   affine brightness                               AffineF32       AffineF32
 //   free intrinsics                                 IntrF32         float
 //   PBA_RECORD_F16_SCALED                           ScaledF16       float
@@ -520,8 +520,9 @@ void launch_geometric(pba_engine* e, const KernelArgs& ka, int mode) {
 //   PBA_RECORD_F32                                  float           float
 // (the half formats are refused with free intrinsics and with affine brightness, and those two with each other unless
 // pba_set_intrinsics_with_affine allows it.)  A cost-only launch stores no record, so only the affine residual — another
-// residual — has a kernel of its own for it; with both switches on every on-device solve refuses, so no cost-only
-// launch is reached and none is compiled for the 26-column tag.
+// residual — has a kernel of its own for it, and with both switches on the 26-column tag has its own too: its validity
+// differs (PFIN: a projection that is not finite makes the block invalid), and the joint solve with free intrinsics
+// (pba_joint_set_solve_intrinsics) must count a candidate's valid blocks as its linearisation does.
 template <class T>
 struct Tag { using type = T; };
 template <int M>
@@ -532,6 +533,8 @@ void dispatch_format(const pba_engine* e, int mode, F&& fn) {
   auto modes = [&](auto tag) {
     if (mode == 1) fn(tag, Mode<1>{});
     else if (mode == 0) fn(tag, Mode<0>{});
+    else if constexpr (RecFormat<typename decltype(tag)::type>::kAffine && RecFormat<typename decltype(tag)::type>::kIntr)
+      fn(Tag<IntrAffineF32>{}, Mode<2>{});
     else if constexpr (RecFormat<typename decltype(tag)::type>::kAffine) fn(Tag<AffineF32>{}, Mode<2>{});
     else fn(Tag<float>{}, Mode<2>{});
   };

@@ -1042,6 +1042,21 @@ struct JointSolve {
   pba::detail::DevBuf<double> poses_new, rho_new, ab_new;
   pba::detail::DevBuf<double> red, red3;
   pba::detail::DevBuf<int> status;
+  // Free intrinsics (pba_joint_set_solve_intrinsics): nc cameras are unknowns, block rows n_frames … n_frames + nc − 1
+  // of the system (0: the keyframes alone).  n_sky_kf: the keyframes' skyline blocks, the first of n_sky.
+  int nc = 0, n_sky_kf = 0;
+  pba::detail::DevBuf<int> cam_ptr, cam_pairs;
+  // the cameras' two-stage sums (pba_joint.hip): chunks of each camera block's Schur terms and of each camera's entries,
+  // their CSR pointers per camera block / per camera, and the partial sums
+  int n_tchunks = 0, n_gchunks = 0;
+  pba::detail::DevBuf<int4> tchunks;
+  pba::detail::DevBuf<int2> gchunks;
+  pba::detail::DevBuf<int> tchunk_ptr, gchunk_ptr;
+  pba::detail::DevBuf<double> tpart, gpart;
+  pba::detail::DevBuf<uint8_t> cstc;                  // per camera: no valid block targets it
+  pba::detail::DevBuf<double> irec, pair_intr, blk_wc, cam_data, gmax_c;
+  pba::detail::DevBuf<double> intr_new_d;             // candidate intrinsics at the active level: camera records …
+  pba::detail::DevBuf<float> intr_new_f;              // … and projection constants
   // The multi-GPU exchange (pba_joint_step_export / import): the plan of the last band K (−1: none) and the summed
   // system's storage over the band profile.  lin_id counts the linearisations; an export stands for the linearisation,
   // λ and band it was made at.  step_band: the last step came from an import (the getters then serve the band storage).
@@ -1094,9 +1109,10 @@ struct pba_engine {
   bool affine = false;               // pba_set_affine_brightness: r = (I − b_t) − E·(I_h − b_h), 18-column records
   pba::detail::DevBuf<double> affine_state;  // its state [a_0 b_0 a_1 b_1 …] (2 per keyframe; zeros after pba_set_frames)
   bool gn_solve_affine = false;      // pba_gn_set_solve_affine: the on-device solve runs at that state, held constant
-  // pba_set_intrinsics_with_affine: opt_intr and affine accept each other (26-column records, evaluation only: every
-  // on-device solve refuses an engine with both on, solve_refuses_both)
+  // pba_set_intrinsics_with_affine: opt_intr and affine accept each other (26-column records; with both on every
+  // on-device solve refuses, solve_refuses_both, but the joint solve under pba_joint_set_solve_intrinsics)
   bool intr_with_affine = false;
+  bool joint_solve_intr = false;     // pba_joint_set_solve_intrinsics: pba_joint_* / pba_solve_joint free the intrinsics too
   pba::detail::DevBuf<float> intr_state;     // its projection constants (8 floats per camera) at the active level
   pba::detail::DevBuf<double> intr_state_d;  // and fp64 camera records (kCamD per camera)
   // photometric engines: the level-0 state as the caller set it (8 per camera); the device copy above is its image at
@@ -1140,9 +1156,10 @@ inline int check_device(pba_engine* e) {
   return PBA_OK;
 }
 
-// Free intrinsics together with affine brightness (pba_set_intrinsics_with_affine) is an evaluation format, the
-// 26-column records: no on-device solve linearises it, whatever pba_gn_set_solve_intrinsics / _affine say.  Every solve
-// entry point asks this before it prepares, plans or moves anything.
+// Free intrinsics together with affine brightness (pba_set_intrinsics_with_affine), the 26-column records: no on-device
+// solve linearises it, whatever pba_gn_set_solve_intrinsics / _affine say — but the joint solve under
+// pba_joint_set_solve_intrinsics, which has its own test (pba_joint.hip ready()).  Every other solve entry point asks
+// this before it prepares, plans or moves anything.
 inline int solve_refuses_both(const pba_engine* e) {
   if (e->opt_intr && e->affine)
     return fail(PBA_ERR_INVALID_ARGUMENT,

@@ -1,5 +1,7 @@
 // pba_joint.hip — the joint solve of poses, inverse distances and affine brightness (include/pba.h pba_joint_*,
-// pba_solve_joint): photometric engines with pba_set_affine_brightness.
+// pba_solve_joint): photometric engines with pba_set_affine_brightness — and, under pba_joint_set_solve_intrinsics, of
+// the target cameras' intrinsics too (engines with pba_set_optimize_intrinsics as well; the second half of the kernels,
+// from joint_intr_moments_kernel on).
 //
 // Unknowns: 8 per keyframe, [δpose (6, T·exp δ) | δa δb], and one δρ per point.  A block (host h, target t, point p) has
 // the rows J = [J_h | J_ab,h | J_t | J_ab,t | J_ρ] and r of the 18·P record.  With Ad the adjoint of T_th,
@@ -50,6 +52,19 @@ __host__ __device__ constexpr int up(int i, int j) { return 10 * i - i * (i - 1)
 static_assert(up(9, 9) == kMom - 1, "upper triangle of 10 columns");
 
 __device__ __forceinline__ double lm_clamp(double d) { return fmin(fmax(d, 1e-6), 1e32); }
+
+// Free intrinsics (pba_joint_set_solve_intrinsics; the layouts are at joint_intr_moments_kernel below)
+constexpr int kColsI = 18;                  // x = [tv tw jr c 1 r | ji(8)]
+constexpr int kCross = 80, kTri = 36;       // ji × x (8×10), upper triangle of ji × ji
+constexpr int kMomI = kMom + kCross + kTri; // 171 moments per block
+constexpr int kIntrRec = 128;               // doubles per block intrinsics record (80 + 36, padded: 1 KB)
+constexpr int kPairIntr = 208;              // doubles per pair: border 8×16, jiᵀwji 8×8 at 128, jiᵀwr at 192, padding
+constexpr int kCam = 80;                    // per camera: direct gradient (8), direct jiᵀwji (8×8, full; the diagonal at 8 + 9r), padding
+constexpr int kCamVals = 73;                // … summed over the camera's pairs: those 72 and the valid blocks
+constexpr int kTermChunk = 1024;            // Schur terms per partial sum of a camera's skyline block
+constexpr int kEntryChunk = 2048;           // entries per partial sum of a camera's gradient
+__host__ __device__ constexpr int up8(int i, int j) { return 8 * i - i * (i - 1) / 2 + (j - i); }  // i ≤ j < 8
+static_assert(up8(7, 7) == kTri - 1, "upper triangle of 8 columns");
 
 // Producer.  The layout of affine_moments_kernel: 8 lanes per block, ⌈P/8⌉ rows per lane (a launch scalar), the
 // fused-state prologue (a.poses), block_affine and photometric_row<…, JAC, …, AFF> — the record path's rows.  Each pass
@@ -337,6 +352,224 @@ __global__ void joint_frame_kernel(const double* __restrict__ pair_rec, const in
   gmax_f[i] = gm;
 }
 
+// ---- free intrinsics (pba_joint_set_solve_intrinsics): poses, ρ, (a, b) and the target cameras' intrinsics -----------
+// Unknowns: the keyframes' 8, then 8 per camera, δk with respect to the level-0 intrinsics state, then δρ.  A block's row
+// gains J_intr = ji (photometric_row<…, INTR, AFF, PFIN>: the 26-column evaluation's row, columns 0–3 with 2^−level), on
+// the camera of its target, so its whole contribution is w·xᵀx over the 18 columns x = [tv tw jr c 1 r | ji(8)].
+// joint_intr_moments_kernel is joint_moments_kernel with those rows and writes two records per block: the 64-double
+// moment record above, byte for byte in its layout (the keyframe kernels run on it as they are), and the intrinsics
+// record, kIntrRec doubles in a second buffer: [0, 80) the cross moments w·ji_a·x_j at 10·a + j, [80, 116) the upper
+// triangle of w·ji_a·ji_b at 80 + up8(a, b), zeros to 128; all zeros for an invalid block.
+// Pair intrinsics record, kPairIntr doubles (joint_intr_pair_kernel): the 8×16 border jiᵀwJ over [pose_h a_h b_h pose_t
+// a_t b_t], row-major; 128 jiᵀwji (8×8, full); 192 jiᵀwr (8).  blk_wc: per block W_c = jiᵀwJ_ρ (8).  Camera data, kCam
+// doubles (joint_cam_kernel): the direct gradient (8) and jiᵀwji (8×8) over the camera's pairs; cstc: 1 for a camera no
+// valid block targets (identity rows, zero gradient, zero step).
+// A rig has few cameras and each sees most of the problem: a camera's diagonal block takes a Schur term from every two
+// blocks of every point, its gradient an entry from every block.  So the cameras' sums run in two fixed stages — partial
+// sums over chunks of the plan's lists (kTermChunk terms, kEntryChunk entries, the camera's pairs dealt to 64 threads),
+// one workgroup each, then the partials in chunk order: still one fixed order, and parallel.
+// The reduced system has n_frames + n_cams block rows, the cameras' with a dense profile behind the keyframes' skyline
+// (pba_joint_plan.h): joint_assemble_kernel and joint_gradient_kernel fill the keyframes' rows as before, the two
+// kernels below the cameras', and joint_solve_kernel factors the whole.
+template <int PM>
+__global__ __launch_bounds__(kBlockThreads) void joint_intr_moments_kernel(const KernelArgs a, double* __restrict__ rec,
+                                                                          double* __restrict__ irec, int ppl) {
+  constexpr int LPB = 8, BPW = kBlockThreads / LPB, NQ = (kMomI + LPB - 1) / LPB;
+  __shared__ __attribute__((aligned(16))) TileBlock s_tb[BPW];
+  __shared__ float2 s_pat[PBA_MAX_PATTERN];
+  __shared__ float s_x[BPW][LPB][kColsI];
+  const int P = a.P;
+  const int blk0 = logical_tile() * BPW;
+  const int lb = threadIdx.x / LPB, k = threadIdx.x % LPB;
+  const int blk = blk0 + lb;
+  const bool live = blk < a.n_blocks;
+  const int bq = live ? blk : a.n_blocks - 1;  // a dead block evaluates the last block, masked below
+  for (int i = threadIdx.x; i < P; i += kBlockThreads) s_pat[i] = make_float2(a.pattern[2 * i], a.pattern[2 * i + 1]);
+  const int pt = stage_tile<LPB>(a, s_tb, lb, k, blk, live);
+  const Affine af = block_affine(a, bq);
+  // this lane's moments m = k, k + 8, … as column pairs (i, j): [0, 55) joint_moments_kernel's, [55, 135) ji_a × x_j,
+  // [135, 171) ji_a × ji_b; a lane past the last moment repeats moment 0 and stores a padding zero
+  unsigned char mi[NQ], mj[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int m = k + LPB * q;
+    int i = 0, j = 0;
+    if (m < kMom) {
+      int rem = m;
+      while (rem >= kCols - i) {
+        rem -= kCols - i;
+        ++i;
+      }
+      j = i + rem;
+    } else if (m < kMom + kCross) {
+      i = kCols + (m - kMom) / kCols;
+      j = (m - kMom) % kCols;
+    } else if (m < kMomI) {
+      int rem = m - kMom - kCross;
+      while (rem >= 8 - i) {
+        rem -= 8 - i;
+        ++i;
+      }
+      j = kCols + i + rem;
+      i += kCols;
+    }
+    mi[q] = (unsigned char)i;
+    mj[q] = (unsigned char)j;
+  }
+  __syncthreads();
+  int okl = 1;
+  float s = 0.0f;
+  double acc[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+  for (int j = 0; j < ppl; ++j) {
+    const int px = k + LPB * j;
+    const bool act = live && px < P;
+    const float Ih = act ? a.host_int[(long long)pt * P + px] : 0.0f;
+    float ji[8];
+    const Row row = photometric_row<PM, true, TileBlock, false, true, true, true>(a, s_tb[lb], s_pat[act ? px : 0], Ih,
+                                                                                  nullptr, ji, &af);
+    const bool use = act && row.ok;
+    okl &= act ? row.ok : 1;
+    s += use ? row.r * row.r : 0.0f;
+    float* x = s_x[lb][k];
+    x[0] = use ? row.tv.x : 0.0f;
+    x[1] = use ? row.tv.y : 0.0f;
+    x[2] = use ? row.tv.z : 0.0f;
+    x[3] = use ? row.tw.x : 0.0f;
+    x[4] = use ? row.tw.y : 0.0f;
+    x[5] = use ? row.tw.z : 0.0f;
+    x[6] = use ? row.jr : 0.0f;
+    x[7] = use ? Ih - af.bh : 0.0f;
+    x[8] = use ? 1.0f : 0.0f;
+    x[9] = use ? row.r : 0.0f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) x[kCols + c] = use ? ji[c] : 0.0f;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+      for (int r = 0; r < LPB; ++r) acc[q] += (double)s_x[lb][r][mi[q]] * (double)s_x[lb][r][mj[q]];
+    __syncthreads();
+  }
+  const int ok = group_all<LPB>(okl);
+  s = group_sum<LPB>(s);
+  const float w = ok ? huber_weight(s, a.huber) : 0.0f;
+  const float bc = ok ? huber_cost(s, a.huber) : 0.0f;
+  if (live) {
+    double* o = rec + (long long)blk * kRec;
+    double* oi = irec + (long long)blk * kIntrRec;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int m = k + LPB * q;
+      const double v = ok ? (double)w * acc[q] : 0.0;
+      if (m < kMom) o[m] = v;
+      else oi[m - kMom] = m < kMomI ? v : 0.0;  // (m < 8·NQ = 176: the padding up to 120)
+    }
+    if (k < kIntrRec - (LPB * NQ - kMom)) oi[LPB * NQ - kMom + k] = 0.0;  // the padding 121 … 127
+    // the tail: 55 w, 56 E, 57 cost, 58 valid, 59…63 zero — one value per lane, lane 7 the last two
+    const double tail = k == 0 ? (double)w : k == 1 ? (ok ? (double)af.E : 0.0) : k == 2 ? (double)bc : k == 3 ? (ok ? 1.0 : 0.0) : 0.0;
+    o[kMom + k] = tail;
+    if (k == LPB - 1) o[kRec - 1] = 0.0;
+  }
+  if (a.wg_red) {
+    const bool one = live && k == 0;
+    wg_reduce2(one ? (double)bc : 0.0, one && ok ? 1.0 : 0.0, a.wg_red + 2 * logical_tile());
+  }
+}
+static_assert(8 * ((kMomI + 7) / 8) - kMom <= kIntrRec && kIntrRec - (8 * ((kMomI + 7) / 8) - kMom) <= 8,
+              "the intrinsics record's padding is written by the moment lanes and one more store per lane");
+
+// One 128-thread workgroup per pair, after joint_pair_kernel (Ad and E are its pair_ad): the intrinsics records of the
+// pair's blocks summed in block order, then the border jiᵀwJ = (Σ w jiᵀx)·M with joint_pair_kernel's map M —
+// jiᵀJ_h = −(jiᵀ[tv tw])·Ad, jiᵀJ_ab,h = [E·jiᵀc, E·jiᵀ1], jiᵀJ_t = jiᵀ[tv tw], jiᵀJ_ab,t = [−E·jiᵀc, −jiᵀ1] — and the
+// pair's jiᵀwji and jiᵀwr.
+__global__ __launch_bounds__(128) void joint_intr_pair_kernel(const double* __restrict__ irec,
+                                                              const int* __restrict__ pair_ptr,
+                                                              const int* __restrict__ pair_blocks,
+                                                              const double* __restrict__ pair_ad,
+                                                              double* __restrict__ pair_intr) {
+  __shared__ double sC[8][kCols], sT[kTri];
+  const int p = blockIdx.x, t = threadIdx.x;
+  if (t < kCross + kTri) {
+    double m = 0.0;
+    for (int q = pair_ptr[p]; q < pair_ptr[p + 1]; ++q) m += irec[(long long)pair_blocks[q] * kIntrRec + t];
+    if (t < kCross) sC[t / kCols][t % kCols] = m;
+    else sT[t - kCross] = m;
+  }
+  __syncthreads();
+  const double* ad = pair_ad + (long long)p * kPairAd;
+  const double E = ad[36];
+  double* o = pair_intr + (long long)p * kPairIntr;
+  {
+    const int r = t / 16, c = t % 16;
+    double v = 0.0;
+    if (c < 6) {
+      for (int q = 0; q < 6; ++q) v += sC[r][q] * ad[q * 6 + c];
+      v = -v;
+    } else if (c == 6) v = E * sC[r][7];
+    else if (c == 7) v = E * sC[r][8];
+    else if (c < 14) v = sC[r][c - 8];
+    else if (c == 14) v = -E * sC[r][7];
+    else v = -sC[r][8];
+    o[t] = v;
+  }
+  if (t < 64) {
+    const int r = t / 8, c = t % 8;
+    o[128 + t] = sT[up8(r < c ? r : c, r < c ? c : r)];
+  }
+  if (t < 16) o[192 + t] = t < 8 ? sC[t][kCols - 1] : 0.0;
+}
+
+// One thread per block: W_c = jiᵀwJ_ρ (8), the cross moments with column jr.
+__global__ void joint_intr_block_kernel(const double* __restrict__ irec, int n_blocks, double* __restrict__ blk_wc) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n_blocks) return;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) blk_wc[(long long)b * 8 + r] = irec[(long long)b * kIntrRec + kCols * r + 6];
+}
+
+// One 64-thread workgroup per camera: the direct gradient and jiᵀwji over its pairs — thread t sums the pairs t, t + 64,
+// … of the list, then thread v sums value v of the 64 partials in thread order — whether a valid block targets it, and
+// its part of the gradient norm, max |g| (a plain parameter block: |k − (k − g)|).
+__global__ __launch_bounds__(64) void joint_cam_kernel(const double* __restrict__ pair_intr,
+                                                        const double* __restrict__ pair_rec,
+                                                        const int* __restrict__ cam_ptr, const int* __restrict__ cam_pairs,
+                                                        double* __restrict__ cam_data, uint8_t* __restrict__ cstc,
+                                                        double* __restrict__ gmax_c) {
+  __shared__ double s_p[64][kCamVals], s_v[kCamVals];
+  const int c = blockIdx.x, t = threadIdx.x;
+  double acc[kCamVals];
+#pragma unroll
+  for (int v = 0; v < kCamVals; ++v) acc[v] = 0.0;
+  for (int q = cam_ptr[c] + t; q < cam_ptr[c + 1]; q += 64) {
+    const int p = cam_pairs[q];
+    const double* pi = pair_intr + (long long)p * kPairIntr;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] += pi[192 + r];
+#pragma unroll
+    for (int v = 0; v < 64; ++v) acc[8 + v] += pi[128 + v];
+    acc[72] += pair_rec[(long long)p * kPairRec + 272];
+  }
+#pragma unroll
+  for (int v = 0; v < kCamVals; ++v) s_p[t][v] = acc[v];
+  __syncthreads();
+  for (int v = t; v < kCamVals; v += 64) {
+    double sum = 0.0;
+    for (int k = 0; k < 64; ++k) sum += s_p[k][v];
+    s_v[v] = sum;
+    if (v < 72) cam_data[(long long)c * kCam + v] = sum;
+  }
+  __syncthreads();
+  if (t == 0) {
+    const bool seen = s_v[72] > 0.0;
+    cstc[c] = seen ? 0 : 1;
+    double gm = 0.0;
+    for (int r = 0; r < 8; ++r) gm = fmax(gm, fabs(s_v[r]));
+    gmax_c[c] = seen ? gm : 0.0;
+  }
+  if (t >= 72 - 64 && t < kCam - 64) cam_data[(long long)c * kCam + 64 + t] = 0.0;  // the padding 72 … 79
+}
+
 // Per point: 1 / H′_ρρ, H′ = H + λ·clamp(H, 1e-6, 1e32); 0 for a point without a valid block (no step).
 __global__ void joint_damp_kernel(const double* __restrict__ pt_data, int n_points, double lambda,
                                   double* __restrict__ inv) {
@@ -411,6 +644,113 @@ __global__ void joint_gradient_kernel(const AsmArgsJ a) {
     v -= w[r] * a.pt_data[(long long)p * kPt + 1] * a.inv[p];
   }
   a.g[u] = a.cst[2 * i + (r >= 6)] ? 0.0 : v;
+}
+
+struct AsmArgsI {
+  AsmArgsJ a;  // sky_i / sky_j, off_*, term_*, fe_* cover the cameras' rows too (pba_joint_plan.h); a.g the whole gradient
+  const double *pair_intr, *cam_data, *blk_wc;
+  const uint8_t* cstc;
+  int n_blocks, n_cams, n_sky_kf;
+  // the two-stage sums: per chunk of Schur terms {skyline block, first term, end, 0} and its 64 partials; per camera's
+  // skyline block (CSR) its chunks; per chunk of a camera's entries {first entry, end} and its 8 partials; per camera
+  // (CSR) its chunks
+  const int4* tchunks;
+  const int* tchunk_ptr;
+  double* tpart;
+  const int2* gchunks;
+  const int* gchunk_ptr;
+  double* gpart;
+};
+
+// entry_w with the third kind of entry: e ≥ n_blocks is block e − n_blocks' camera part W_c
+__device__ __forceinline__ const double* entry_w3(const AsmArgsI& x, int e, int* p) {
+  if (e >= x.n_blocks) {
+    *p = x.a.block_point[e - x.n_blocks];
+    return x.blk_wc + (long long)(e - x.n_blocks) * 8;
+  }
+  return entry_w(x.a, e, p);
+}
+
+// One 64-thread workgroup per chunk of a camera block's Schur terms, thread = element (r, c): Σ W_a W_bᵀ/H′_ρρ over
+// the chunk's terms in list order.
+__global__ __launch_bounds__(64) void joint_intr_terms_kernel(const AsmArgsI x) {
+  const AsmArgsJ& a = x.a;
+  const int4 ch = x.tchunks[blockIdx.x];
+  const int t = threadIdx.x, r = t >> 3, c = t & 7;
+  double v = 0.0;
+  for (int q = ch.y; q < ch.z; ++q) {
+    const int2 tm = a.terms[q];
+    int p, p2;
+    const double* wa = entry_w3(x, tm.x, &p);
+    const double* wb = entry_w3(x, tm.y, &p2);
+    v += wa[r] * wb[c] * a.inv[p];
+  }
+  x.tpart[(long long)blockIdx.x * 64 + t] = v;
+}
+
+// One 64-thread workgroup per chunk of a camera's entries: Σ W_c·g_ρ/H′_ρρ — thread t the entries t, t + 64, … of the
+// chunk, then thread r < 8 sums row r of the 64 partials in thread order.
+__global__ __launch_bounds__(64) void joint_intr_gradient_parts_kernel(const AsmArgsI x) {
+  __shared__ double s_p[64][8];
+  const AsmArgsJ& a = x.a;
+  const int2 ch = x.gchunks[blockIdx.x];
+  const int t = threadIdx.x;
+  double acc[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) acc[r] = 0.0;
+  for (int q = ch.x + t; q < ch.y; q += 64) {
+    int p;
+    const double* w = entry_w3(x, a.fe_entries[q], &p);
+    const double f = a.pt_data[(long long)p * kPt + 1] * a.inv[p];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc[r] += w[r] * f;
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) s_p[t][r] = acc[r];
+  __syncthreads();
+  if (t < 8) {
+    double sum = 0.0;
+    for (int k = 0; k < 64; ++k) sum += s_p[k][t];
+    x.gpart[(long long)blockIdx.x * 8 + t] = sum;
+  }
+}
+
+// joint_assemble_kernel for the cameras' rows: one 64-thread workgroup per skyline block (n_frames + c, j) — the border
+// parts of camera c's pairs that touch keyframe j in list order, or the camera's jiᵀwji on the diagonal
+// (joint_cam_kernel); then the block's Schur partials (joint_intr_terms_kernel) in chunk order; then the damping and the
+// constants (camera c without a valid block, the column's keyframe half or camera).
+__global__ __launch_bounds__(64) void joint_intr_assemble_kernel(const AsmArgsI x) {
+  const AsmArgsJ& a = x.a;
+  const int s = x.n_sky_kf + blockIdx.x, t = threadIdx.x, r = t >> 3, c = t & 7;
+  const int i = a.sky_i[s], j = a.sky_j[s], cam = i - a.n_frames;
+  double v = 0.0;
+  if (j < a.n_frames) {
+    for (int q = a.off_ptr[s]; q < a.off_ptr[s + 1]; ++q) {
+      const int e = a.off_pairs[q];
+      v += x.pair_intr[(long long)(e >> 1) * kPairIntr + r * 16 + ((e & 1) ? 8 : 0) + c];
+    }
+  } else if (i == j) {
+    v = x.cam_data[(long long)cam * kCam + 8 + t];
+  }
+  for (int q = x.tchunk_ptr[blockIdx.x]; q < x.tchunk_ptr[blockIdx.x + 1]; ++q) v -= x.tpart[(long long)q * 64 + t];
+  const bool ci = x.cstc[cam] != 0;
+  const bool cj = j < a.n_frames ? a.cst[2 * j + (c >= 6)] != 0 : x.cstc[j - a.n_frames] != 0;
+  if (ci || cj) v = i == j && r == c ? 1.0 : 0.0;
+  else if (i == j && r == c) v += a.lambda * lm_clamp(x.cam_data[(long long)cam * kCam + 8 + 9 * r]);
+  a.S[(long long)s * 64 + t] = v;
+  a.L[(long long)s * 64 + t] = v;
+}
+
+// One thread per camera unknown: g_S = g − Σ W_c·g_ρ/H′_ρρ, the camera's partials (joint_intr_gradient_parts_kernel) in
+// chunk order; 0 for a constant.
+__global__ void joint_intr_gradient_kernel(const AsmArgsI x) {
+  const AsmArgsJ& a = x.a;
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= 8 * x.n_cams) return;
+  const int cam = u >> 3, r = u & 7;
+  double v = x.cam_data[(long long)cam * kCam + r];
+  for (int q = x.gchunk_ptr[cam]; q < x.gchunk_ptr[cam + 1]; ++q) v -= x.gpart[(long long)q * 8 + r];
+  a.g[8 * a.n_frames + u] = x.cstc[cam] ? 0.0 : v;
 }
 
 // ---- the reduced solve: S δ = −g, S = LLᵀ in place (8×8-block skyline, right-looking), one workgroup ----------------
@@ -667,6 +1007,129 @@ __global__ __launch_bounds__(256) void joint_update_kernel(const UpdArgs a) {
   wg_reduce_sum_max<3>(v, 0.0, slot, r + 3);
 }
 
+struct UpdArgsI {
+  UpdArgs u;  // x holds the keyframes' steps, then the cameras'
+  const double *blk_wc, *cam_data, *kcur;  // kcur: the intrinsics state's camera records at the active level
+  const uint8_t* cstc;
+  double* knew_d;  // the candidate's camera records at the active level …
+  float* knew_f;   // … and its projection constants (8 floats per camera): launch_cost_only's two buffers
+  int n_cams;
+  double kscale;   // 2^−level: entries 0–3 of the level's image move by 2^−level·δk, the distortion by δk
+};
+
+// joint_update_kernel with free intrinsics: δρ's sum runs over the point's camera entries too (after its blocks'
+// target parts, the entry order), and threads [n_points + n_frames, n_points + n_frames + n_cams) form the candidate
+// intrinsics k + δk as the level's camera record [k(8) | cx cy 1/fx 1/fy p1…p4] (upload_cameras' layout) and its fp32
+// copy.  The cameras' parts of the three sums go into the same slots: the model decrease over the 8 unknowns of a camera
+// with a valid block, and ‖δk‖², ‖k + δk‖² of the level-0 state.
+__global__ __launch_bounds__(256) void joint_intr_update_kernel(const UpdArgsI x) {
+  const UpdArgs& a = x.u;
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  double v[3] = {0.0, 0.0, 0.0};
+  if (*a.status == 0) {
+    if (u < a.n_points) {
+      const double* pd = a.pt_data + (long long)u * kPt;
+      const double inv = a.inv[u];
+      const int q0 = a.pt_ptr[u], q1 = a.pt_ptr[u + 1];
+      double d = 0.0;
+      if (inv > 0.0) {
+        double acc = pd[1];
+        const double* xh = a.x + 8 * a.point_host[u];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) acc += pd[4 + r] * xh[r];
+        for (int q = q0; q < q1; ++q) {
+          const int b = a.pt_blocks[q];
+          const double* w = a.blk_data + (long long)b * kBlk + 2;
+          const double* xt = a.x + 8 * a.block_rec[b].z;
+#pragma unroll
+          for (int r = 0; r < 8; ++r) acc += w[r] * xt[r];
+        }
+        for (int q = q0; q < q1; ++q) {
+          const int b = a.pt_blocks[q];
+          const double* w = x.blk_wc + (long long)b * 8;
+          const double* xc = a.x + 8 * (a.n_frames + (a.block_rec[b].w & 0xffff));
+#pragma unroll
+          for (int r = 0; r < 8; ++r) acc += w[r] * xc[r];
+        }
+        d = -acc * inv;
+        v[0] = a.lambda * lm_clamp(pd[0]) * d * d - pd[1] * d;
+      }
+      const double rn = a.rho[u] + d;
+      a.drho[u] = d;
+      a.rho_new[u] = rn;
+      if (q1 > q0) {
+        v[1] = d * d;
+        v[2] = rn * rn;
+      }
+    } else if (u < a.n_points + a.n_frames) {
+      const int i = u - a.n_points;
+      const double* fd = a.frame_data + (long long)i * kFrame;
+      const bool cp = a.cst[2 * i] != 0, ca = a.cst[2 * i + 1] != 0;
+      double d[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        d[r] = (r < 6 ? cp : ca) ? 0.0 : a.x[8 * i + r];
+        if (!(r < 6 ? cp : ca)) v[0] += a.lambda * lm_clamp(fd[8 + r]) * d[r] * d[r] - fd[r] * d[r];
+      }
+      double T[7], Tn[7];
+#pragma unroll
+      for (int r = 0; r < 7; ++r) T[r] = Tn[r] = a.poses[7 * i + r];
+      if (!cp) {
+        se3_exp_mul(T, d, Tn);
+#pragma unroll
+        for (int r = 0; r < 7; ++r) {
+          v[1] += (Tn[r] - T[r]) * (Tn[r] - T[r]);
+          v[2] += Tn[r] * Tn[r];
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 7; ++r) a.poses_new[7 * i + r] = Tn[r];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const double o = a.ab[2 * i + r], n = ca ? o : o + d[6 + r];
+        a.ab_new[2 * i + r] = n;
+        if (!ca) {
+          v[1] += d[6 + r] * d[6 + r];
+          v[2] += n * n;
+        }
+      }
+    } else if (u < a.n_points + a.n_frames + x.n_cams) {
+      const int c = u - a.n_points - a.n_frames;
+      const double* cd = x.cam_data + (long long)c * kCam;
+      const bool cc = x.cstc[c] != 0;
+      double kn[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const double d = cc ? 0.0 : a.x[8 * (a.n_frames + c) + r];
+        const double k = x.kcur[kCamD * c + r];
+        kn[r] = cc ? k : k + (r < 4 ? x.kscale * d : d);
+        if (!cc) {
+          // the level-0 state's entry (upload_intrinsics_state's map inverted; the level's own at level 0)
+          const double k0 = x.kscale == 1.0 || r >= 4 ? k : r < 2 ? k / x.kscale : (k + 0.5) / x.kscale - 0.5;
+          v[0] += a.lambda * lm_clamp(cd[8 + 9 * r]) * d * d - cd[r] * d;
+          v[1] += d * d;
+          v[2] += (k0 + d) * (k0 + d);
+        }
+      }
+      double* od = x.knew_d + (long long)kCamD * c;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        od[r] = kn[r];
+        x.knew_f[8 * c + r] = (float)kn[r];
+      }
+      od[8] = kn[2];
+      od[9] = kn[3];
+      od[10] = 1.0 / kn[0];
+      od[11] = 1.0 / kn[1];
+#pragma unroll
+      for (int r = 4; r < 8; ++r) od[8 + r] = kn[r];
+    }
+  }
+  double* const r = a.red3 + 4 * blockIdx.x;
+  double* const slot[3] = {r, r + 1, r + 2};
+  wg_reduce_sum_max<3>(v, 0.0, slot, r + 3);
+}
+
 // ---- the multi-GPU exchange (pba.h pba_joint_step_export / import; the layout: pba_joint_plan.h) ---------------------
 struct ExArgsJ {
   AsmArgsJ a;      // the sources; its cst, S, L, g and lambda are not read
@@ -865,19 +1328,27 @@ __global__ __launch_bounds__(256) void joint_update_parts_kernel(const UpdArgs a
   wg_reduce_sum_max<6>(v, 0.0, slot, r + 6);
 }
 
-int ready(pba_engine* e) {
+// intr_ok: the entry point runs with free intrinsics under pba_joint_set_solve_intrinsics (the single-GPU ones); the
+// multi-GPU exchange refuses them either way.
+int ready(pba_engine* e, bool intr_ok = false) {
   if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
   if (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC || !e->affine)
     return fail(PBA_ERR_INVALID_ARGUMENT, "the joint solve needs a photometric engine with pba_set_affine_brightness");
-  if (e->opt_intr)
-    return fail(PBA_ERR_INVALID_ARGUMENT, "the joint solve does not combine with pba_set_optimize_intrinsics");
+  if (e->opt_intr && !(intr_ok && e->joint_solve_intr))
+    return fail(PBA_ERR_INVALID_ARGUMENT,
+                intr_ok ? "the joint solve frees the intrinsics of pba_set_optimize_intrinsics only with pba_joint_set_solve_intrinsics"
+                        : "the multi-GPU joint solve does not combine with pba_set_optimize_intrinsics");
   if (e->n_blocks <= 0) return fail(PBA_ERR_NOT_READY, "pba_set_blocks first");
   if (!e->state_set) return fail(PBA_ERR_NOT_READY, "pba_set_state first");
   if (!e->have_images || e->P <= 0) return fail(PBA_ERR_NOT_READY, "images/pattern missing");
   if (int rc = check_device(e)) return rc;
   JointSolve& J = e->joint;
+  const int nc = e->opt_intr ? e->n_cams : 0;  // cameras among the unknowns
+  if (J.planned && J.nc != nc) J.planned = false;
   if (!J.planned) {
     JointPlanInput in;
+    in.n_cams = nc;
+    in.frame_cam = e->frame_cam_h.data();
     in.n_frames = e->n_frames;
     in.n_pairs = e->n_pairs;
     in.n_points = e->n_points;
@@ -889,9 +1360,9 @@ int ready(pba_engine* e) {
     in.point_host = e->point_host_h.data();
     JointPlan P;
     if (!build_joint_plan(in, P)) return fail(PBA_ERR_INVALID_ARGUMENT, "inconsistent pairs (or a block whose target is its host)");
-    const int nf = e->n_frames;
+    const int nf = e->n_frames, N = nf + nc;
     std::vector<int> si(P.n_sky), sj(P.n_sky);
-    for (int i = 0; i < nf; ++i)
+    for (int i = 0; i < N; ++i)
       for (int j = P.first[i]; j <= i; ++j) {
         si[P.row[i] + (j - P.first[i])] = i;
         sj[P.row[i] + (j - P.first[i])] = j;
@@ -916,14 +1387,42 @@ int ready(pba_engine* e) {
     PBA_HIP(J.fe_entries.upload(P.fe_entries, e->stream));
     PBA_HIP(J.sky_i.upload(si, e->stream));
     PBA_HIP(J.sky_j.upload(sj, e->stream));
+    if (nc > 0) {
+      PBA_HIP(J.cam_ptr.upload(P.cam_ptr, e->stream));
+      PBA_HIP(J.cam_pairs.upload(P.cam_pairs, e->stream));
+      // the chunks of the cameras' two-stage sums: of each camera block's Schur terms, of each camera's entries
+      std::vector<int4> tch;
+      std::vector<int2> gch;
+      std::vector<int> tptr(1, 0), gptr(1, 0);
+      for (int s = P.n_sky_kf; s < P.n_sky; ++s) {
+        for (int q = P.term_ptr[s]; q < P.term_ptr[s + 1]; q += kTermChunk)
+          tch.push_back(make_int4(s, q, std::min(q + kTermChunk, P.term_ptr[s + 1]), 0));
+        tptr.push_back((int)tch.size());
+      }
+      for (int c = 0; c < nc; ++c) {
+        for (int q = P.fe_ptr[nf + c]; q < P.fe_ptr[nf + c + 1]; q += kEntryChunk)
+          gch.push_back(make_int2(q, std::min(q + kEntryChunk, P.fe_ptr[nf + c + 1])));
+        gptr.push_back((int)gch.size());
+      }
+      J.n_tchunks = (int)tch.size();
+      J.n_gchunks = (int)gch.size();
+      PBA_HIP(J.tchunks.upload(tch, e->stream));
+      PBA_HIP(J.gchunks.upload(gch, e->stream));
+      PBA_HIP(J.tchunk_ptr.upload(tptr, e->stream));
+      PBA_HIP(J.gchunk_ptr.upload(gptr, e->stream));
+      PBA_HIP(J.tpart.resize(64 * (size_t)std::max(J.n_tchunks, 1)));
+      PBA_HIP(J.gpart.resize(8 * (size_t)std::max(J.n_gchunks, 1)));
+    }
     PBA_HIP(hipStreamSynchronize(e->stream));  // (the plan's vectors die with this scope)
     J.n_sky = P.n_sky;
+    J.n_sky_kf = P.n_sky_kf;
+    J.nc = nc;
     J.first_h = P.first;
     J.row_h = P.row;
     const size_t nb = e->n_blocks, npt = e->n_points, np = std::max(e->n_pairs, 1);
     J.lin_slots = (int)((nb * 8 + kBlockThreads - 1) / kBlockThreads);
     J.pt_slots = (int)((npt + 255) / 256);
-    J.upd_slots = (int)((npt + nf + 255) / 256);
+    J.upd_slots = (int)((npt + N + 255) / 256);
     PBA_HIP(J.rec.resize(nb * kRec));
     PBA_HIP(J.pair_rec.resize(np * kPairRec));
     PBA_HIP(J.pair_ad.resize(np * kPairAd));
@@ -936,9 +1435,9 @@ int ready(pba_engine* e) {
     PBA_HIP(J.cst.resize(2 * (size_t)nf));
     PBA_HIP(J.S.resize(64 * (size_t)J.n_sky));
     PBA_HIP(J.L.resize(64 * (size_t)J.n_sky));
-    PBA_HIP(J.Linv.resize(64 * (size_t)nf));
-    PBA_HIP(J.g.resize(8 * (size_t)nf));
-    PBA_HIP(J.x.resize(8 * (size_t)nf));
+    PBA_HIP(J.Linv.resize(64 * (size_t)N));
+    PBA_HIP(J.g.resize(8 * (size_t)N));
+    PBA_HIP(J.x.resize(8 * (size_t)N));
     PBA_HIP(J.drho.resize(npt));
     PBA_HIP(J.poses_new.resize(7 * (size_t)nf));
     PBA_HIP(J.rho_new.resize(npt));
@@ -946,6 +1445,16 @@ int ready(pba_engine* e) {
     PBA_HIP(J.red.resize(2 * (nb / 16 + 2)));
     PBA_HIP(J.red3.resize(4 * (size_t)J.upd_slots));
     PBA_HIP(J.status.resize(1));
+    if (nc > 0) {
+      PBA_HIP(J.irec.resize(nb * kIntrRec));
+      PBA_HIP(J.pair_intr.resize(np * kPairIntr));
+      PBA_HIP(J.blk_wc.resize(nb * 8));
+      PBA_HIP(J.cam_data.resize((size_t)nc * kCam));
+      PBA_HIP(J.gmax_c.resize(nc));
+      PBA_HIP(J.cstc.resize(nc));
+      PBA_HIP(J.intr_new_d.resize((size_t)nc * kCamD));
+      PBA_HIP(J.intr_new_f.resize((size_t)nc * 8));
+    }
     J.planned = true;
     J.linearized = J.have_step = false;
     J.ex_K = -1;  // (the exchange plan is the profile's)
@@ -968,7 +1477,10 @@ int linearize_j(pba_engine* e, double* cost) {
   ka.wg_red = J.red.p;
   const int grid = J.lin_slots;
   dispatch_pm(e, [&](auto pm) {
-    joint_moments_kernel<decltype(pm)::value><<<grid, kBlockThreads, 0, e->stream>>>(ka, J.rec.p, (e->P + 7) / 8);
+    if (J.nc > 0)  // (ka's target intrinsics are the state's: make_kernel_args)
+      joint_intr_moments_kernel<decltype(pm)::value><<<grid, kBlockThreads, 0, e->stream>>>(ka, J.rec.p, J.irec.p, (e->P + 7) / 8);
+    else
+      joint_moments_kernel<decltype(pm)::value><<<grid, kBlockThreads, 0, e->stream>>>(ka, J.rec.p, (e->P + 7) / 8);
   });
   PBA_HIP(hipGetLastError());
   if (e->n_pairs > 0)
@@ -982,6 +1494,14 @@ int linearize_j(pba_engine* e, double* cost) {
   joint_frame_kernel<<<(nf + 255) / 256, 256, 0, e->stream>>>(J.pair_rec.p, J.frame_ptr.p, J.frame_pairs.p, J.fixed.p,
                                                              e->poses.p, e->affine_state.p, nf, J.frame_data.p, J.cst.p,
                                                              J.gmax_f.p);
+  if (J.nc > 0) {
+    if (e->n_pairs > 0)
+      joint_intr_pair_kernel<<<e->n_pairs, 128, 0, e->stream>>>(J.irec.p, J.pair_ptr.p, J.pair_blocks.p, J.pair_ad.p,
+                                                                J.pair_intr.p);
+    joint_intr_block_kernel<<<(e->n_blocks + 255) / 256, 256, 0, e->stream>>>(J.irec.p, e->n_blocks, J.blk_wc.p);
+    joint_cam_kernel<<<J.nc, 64, 0, e->stream>>>(J.pair_intr.p, J.pair_rec.p, J.cam_ptr.p, J.cam_pairs.p, J.cam_data.p,
+                                                 J.cstc.p, J.gmax_c.p);
+  }
   PBA_HIP(hipGetLastError());
   J.linearized = true;
   J.have_step = false;
@@ -999,9 +1519,12 @@ int gradient_norm(pba_engine* e, double* gmax) {
   PBA_HIP(hipMemcpyAsync(f.data(), J.gmax_f.p, sizeof(double) * f.size(), hipMemcpyDeviceToHost, e->stream));
   if (J.pt_slots > 0)
     PBA_HIP(hipMemcpyAsync(p.data(), J.gmax_p.p, sizeof(double) * 2 * (size_t)J.pt_slots, hipMemcpyDeviceToHost, e->stream));
+  std::vector<double> c(J.nc);
+  if (J.nc > 0) PBA_HIP(hipMemcpyAsync(c.data(), J.gmax_c.p, sizeof(double) * c.size(), hipMemcpyDeviceToHost, e->stream));
   PBA_HIP(hipStreamSynchronize(e->stream));
   double g = 0.0;
   for (double v : f) g = std::max(g, v);
+  for (double v : c) g = std::max(g, v);
   for (int s = 0; s < J.pt_slots; ++s) g = std::max(g, p[2 * s + 1]);
   *gmax = g;
   return PBA_OK;
@@ -1014,14 +1537,26 @@ int step_j(pba_engine* e, double lambda, double* model, int* status, double* sq_
   AsmArgsJ aa{J.pair_rec.p, J.blk_data.p, J.pt_data.p, J.inv.p, J.frame_data.p, J.frame_ptr.p, J.frame_pairs.p,
               J.off_ptr.p, J.off_pairs.p, J.term_ptr.p, J.fe_ptr.p, J.fe_entries.p, J.sky_i.p, J.sky_j.p,
               e->block_point.p, J.terms.p, J.cst.p, J.S.p, J.L.p, J.g.p, nf, J.n_sky, lambda};
-  joint_assemble_kernel<<<J.n_sky, 64, 0, e->stream>>>(aa);
+  joint_assemble_kernel<<<J.nc > 0 ? J.n_sky_kf : J.n_sky, 64, 0, e->stream>>>(aa);
   joint_gradient_kernel<<<(8 * nf + 255) / 256, 256, 0, e->stream>>>(aa);
-  SolveArgsJ so{J.L.p, J.first.p, J.row.p, J.g.p, J.Linv.p, J.x.p, J.status.p, nf, J.colptr.p, J.colrows.p};
+  const AsmArgsI ai{aa, J.pair_intr.p, J.cam_data.p, J.blk_wc.p, J.cstc.p, e->n_blocks, J.nc, J.n_sky_kf, J.tchunks.p,
+                    J.tchunk_ptr.p, J.tpart.p, J.gchunks.p, J.gchunk_ptr.p, J.gpart.p};
+  if (J.nc > 0) {
+    if (J.n_tchunks > 0) joint_intr_terms_kernel<<<J.n_tchunks, 64, 0, e->stream>>>(ai);
+    if (J.n_gchunks > 0) joint_intr_gradient_parts_kernel<<<J.n_gchunks, 64, 0, e->stream>>>(ai);
+    joint_intr_assemble_kernel<<<J.n_sky - J.n_sky_kf, 64, 0, e->stream>>>(ai);
+    joint_intr_gradient_kernel<<<(8 * J.nc + 63) / 64, 64, 0, e->stream>>>(ai);
+  }
+  SolveArgsJ so{J.L.p, J.first.p, J.row.p, J.g.p, J.Linv.p, J.x.p, J.status.p, nf + J.nc, J.colptr.p, J.colrows.p};
   joint_solve_kernel<<<1, 256, 0, e->stream>>>(so);
   UpdArgs ua{J.x.p, J.pt_data.p, J.blk_data.p, J.inv.p, J.frame_data.p, e->poses.p, e->rho.p, e->affine_state.p,
              J.pt_ptr.p, J.pt_blocks.p, e->point_host_d.p, J.status.p, e->block_rec.p, J.cst.p, J.drho.p,
              J.poses_new.p, J.rho_new.p, J.ab_new.p, J.red3.p, npt, nf, lambda};
-  joint_update_kernel<<<J.upd_slots, 256, 0, e->stream>>>(ua);
+  if (J.nc > 0)
+    joint_intr_update_kernel<<<J.upd_slots, 256, 0, e->stream>>>(UpdArgsI{
+        ua, J.blk_wc.p, J.cam_data.p, e->intr_state_d.p, J.cstc.p, J.intr_new_d.p, J.intr_new_f.p, J.nc, std::ldexp(1.0, -e->level)});
+  else
+    joint_update_kernel<<<J.upd_slots, 256, 0, e->stream>>>(ua);
   PBA_HIP(hipGetLastError());
   int st = 0;
   std::vector<double> h(4 * (size_t)J.upd_slots);
@@ -1046,7 +1581,8 @@ int step_j(pba_engine* e, double lambda, double* model, int* status, double* sq_
 int candidate_cost_j(pba_engine* e, double* cost, double* n_valid) {
   JointSolve& J = e->joint;
   int slots = 0;
-  if (int rc = launch_cost_only(e, e->pairs.p, J.rho_new.p, J.red.p, &slots, J.poses_new.p, nullptr, nullptr, J.ab_new.p))
+  if (int rc = launch_cost_only(e, e->pairs.p, J.rho_new.p, J.red.p, &slots, J.poses_new.p,
+                                J.nc > 0 ? J.intr_new_f.p : nullptr, J.nc > 0 ? J.intr_new_d.p : nullptr, J.ab_new.p))
     return rc;
   return sum_red(e, J.red.p, slots, cost, n_valid);
 }
@@ -1057,6 +1593,11 @@ int accept_j(pba_engine* e) {
   PBA_HIP(hipMemcpyAsync(e->poses.p, J.poses_new.p, sizeof(double) * 7 * nf, hipMemcpyDeviceToDevice, e->stream));
   PBA_HIP(hipMemcpyAsync(e->rho.p, J.rho_new.p, sizeof(double) * (size_t)e->n_points, hipMemcpyDeviceToDevice, e->stream));
   PBA_HIP(hipMemcpyAsync(e->affine_state.p, J.ab_new.p, sizeof(double) * 2 * nf, hipMemcpyDeviceToDevice, e->stream));
+  if (J.nc > 0) {  // the intrinsics state at the active level, then its level-0 copy on the host (pba_get_intrinsics)
+    PBA_HIP(hipMemcpyAsync(e->intr_state_d.p, J.intr_new_d.p, sizeof(double) * kCamD * (size_t)J.nc, hipMemcpyDeviceToDevice, e->stream));
+    PBA_HIP(hipMemcpyAsync(e->intr_state.p, J.intr_new_f.p, sizeof(float) * 8 * (size_t)J.nc, hipMemcpyDeviceToDevice, e->stream));
+    if (int rc = download_intrinsics_state(e)) return rc;
+  }
   J.linearized = J.have_step = false;
   e->aff.linearized = e->aff.have_step = false;
   e->pairs_fresh = false;
@@ -1188,20 +1729,29 @@ int exported(pba_engine* e, double lambda, int K) {
 
 extern "C" {
 
+int pba_joint_set_solve_intrinsics(pba_engine* e, int32_t enable) {
+  if (!e) return fail(PBA_ERR_INVALID_ARGUMENT, "null engine");
+  if (enable && (e->opt.residual_kind != PBA_RESIDUAL_PHOTOMETRIC || !e->opt_intr || !e->affine))
+    return fail(PBA_ERR_INVALID_ARGUMENT,
+                "pba_joint_set_solve_intrinsics needs pba_set_optimize_intrinsics and pba_set_affine_brightness");
+  e->joint_solve_intr = enable != 0;
+  return PBA_OK;
+}
+
 int pba_joint_linearize(pba_engine* e, double* cost) {
-  if (int rc = ready(e)) return rc;
+  if (int rc = ready(e, true)) return rc;
   return linearize_j(e, cost);
 }
 
 int pba_joint_system_size(pba_engine* e, int32_t* n) {
-  if (int rc = ready(e)) return rc;
+  if (int rc = ready(e, true)) return rc;
   if (!n) return fail(PBA_ERR_INVALID_ARGUMENT, "null size");
-  *n = 8 * e->n_frames;
+  *n = 8 * (e->n_frames + e->joint.nc);  // keyframes first, then the cameras of pba_joint_set_solve_intrinsics
   return PBA_OK;
 }
 
 int pba_joint_step(pba_engine* e, double lambda, double* model_decrease, int32_t* solver_status) {
-  if (int rc = ready(e)) return rc;
+  if (int rc = ready(e, true)) return rc;
   if (!(lambda >= 0.0)) return fail(PBA_ERR_INVALID_ARGUMENT, "lambda must be >= 0");
   if (!e->joint.linearized) return fail(PBA_ERR_NOT_READY, "pba_joint_linearize first");
   int st = 0;
@@ -1211,10 +1761,10 @@ int pba_joint_step(pba_engine* e, double lambda, double* model_decrease, int32_t
 }
 
 int pba_joint_get_reduced_system(pba_engine* e, double* S_dense, double* g) {
-  if (int rc = ready(e)) return rc;
+  if (int rc = ready(e, true)) return rc;
   JointSolve& J = e->joint;
   if (!J.linearized || !J.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
-  const int nf = e->n_frames;
+  const int nf = e->n_frames + J.nc;  // block rows
   const size_t n = 8 * (size_t)nf;
   if (S_dense) {  // after an import: the summed system over the band profile
     std::vector<double> S((size_t)64 * (J.step_band ? J.ex_n_sky : J.n_sky));
@@ -1233,7 +1783,7 @@ int pba_joint_get_reduced_system(pba_engine* e, double* S_dense, double* g) {
 }
 
 int pba_joint_get_step(pba_engine* e, double* d_keyframes, double* d_inv_dist) {
-  if (int rc = ready(e)) return rc;
+  if (int rc = ready(e, true)) return rc;
   JointSolve& J = e->joint;
   if (!J.linearized || !J.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
   if (d_keyframes)
@@ -1244,8 +1794,21 @@ int pba_joint_get_step(pba_engine* e, double* d_keyframes, double* d_inv_dist) {
   return PBA_OK;
 }
 
+int pba_joint_get_intrinsics_step(pba_engine* e, double* d_intrinsics) {
+  if (int rc = ready(e, true)) return rc;
+  JointSolve& J = e->joint;
+  if (J.nc <= 0) return fail(PBA_ERR_INVALID_ARGUMENT, "pba_joint_set_solve_intrinsics first");
+  if (!J.linearized || !J.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
+  if (d_intrinsics) {
+    PBA_HIP(hipMemcpyAsync(d_intrinsics, J.x.p + 8 * (size_t)e->n_frames, sizeof(double) * 8 * (size_t)J.nc,
+                           hipMemcpyDeviceToHost, e->stream));
+    PBA_HIP(hipStreamSynchronize(e->stream));
+  }
+  return PBA_OK;
+}
+
 int pba_joint_candidate_cost(pba_engine* e, double* cost) {
-  if (int rc = ready(e)) return rc;
+  if (int rc = ready(e, true)) return rc;
   if (!cost) return fail(PBA_ERR_INVALID_ARGUMENT, "null cost");
   if (!e->joint.linearized || !e->joint.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
   double nv = 0.0;
@@ -1253,7 +1816,7 @@ int pba_joint_candidate_cost(pba_engine* e, double* cost) {
 }
 
 int pba_joint_accept(pba_engine* e) {
-  if (int rc = ready(e)) return rc;
+  if (int rc = ready(e, true)) return rc;
   if (!e->joint.linearized || !e->joint.have_step) return fail(PBA_ERR_NOT_READY, "pba_joint_step first");
   return accept_j(e);
 }
@@ -1261,7 +1824,7 @@ int pba_joint_accept(pba_engine* e) {
 // The host-driven trust-region loop (pba_host_lm.h); norms over the free poses (ambient [q | t]), the ρ of points with
 // blocks and the free (a, b).  ‖x‖ after an accepted step is its candidate's, from the step's ‖candidate‖².
 int pba_solve_joint(pba_engine* e, const pba_solver_options* o, pba_solver_summary* sum) {
-  if (int rc = ready(e)) return rc;
+  if (int rc = ready(e, true)) return rc;
   double sq_x = 0.0;
   HostLmStages stages{
       [&](double* cost, double* gmax, double* x_norm) {

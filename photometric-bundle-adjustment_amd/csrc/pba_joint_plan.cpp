@@ -11,7 +11,10 @@ namespace detail {
 
 bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
   const int nf = in.n_frames, np = in.n_pairs, npt = in.n_points, nb = in.n_blocks;
-  if (nf <= 0 || np < 0 || npt < 0 || nb < 0) return false;
+  const int nc = in.n_cams, N = nf + (nc > 0 ? nc : 0);  // block rows: keyframes, then cameras
+  if (nf <= 0 || np < 0 || npt < 0 || nb < 0 || nc < 0) return false;
+  for (int f = 0; nc > 0 && f < nf; ++f)
+    if (!in.frame_cam || in.frame_cam[f] < 0 || in.frame_cam[f] >= nc) return false;
   for (int p = 0; p < np; ++p) {
     if (in.pair_host[p] < 0 || in.pair_host[p] >= nf || in.pair_target[p] < 0 || in.pair_target[p] >= nf) return false;
     if (in.pair_host[p] == in.pair_target[p]) return false;
@@ -27,7 +30,7 @@ bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
   frame_pair_lists(nf, np, in.pair_host, in.pair_target, P.frame_ptr, P.frame_pairs);
   auto target_of = [&](int b) { return in.pair_target[in.block_pair[b]]; };
   // skyline profile: every two keyframes of one point share a block of the reduced system
-  P.first.resize(nf);
+  P.first.assign(N, 0);  // (a camera's row starts at keyframe 0)
   for (int f = 0; f < nf; ++f) P.first[f] = f;
   for (int q = 0; q < npt; ++q) {
     if (P.pt_ptr[q] == P.pt_ptr[q + 1]) continue;
@@ -40,15 +43,52 @@ bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
     }
   }
   skyline_profile(P.first, P.row, P.last, P.colptr, P.colrows);
-  P.n_sky = P.row[nf];
+  P.n_sky = P.row[N];
+  P.n_sky_kf = P.row[nf];
   auto sky = [&](int i, int j) { return P.row[i] + (j - P.first[i]); };  // i ≥ j ≥ first[i]
   // (self pairs are refused above; a pair without blocks lies in no point's span, so it takes no part)
-  off_diagonal_pair_lists(np, in.pair_host, in.pair_target, P.first, P.row,
-                          [&](int p) { return P.pair_ptr[p] < P.pair_ptr[p + 1]; }, P.off_ptr, P.off_pairs);
+  auto has_blocks = [&](int p) { return P.pair_ptr[p] < P.pair_ptr[p + 1]; };
+  off_diagonal_pair_lists(np, in.pair_host, in.pair_target, P.first, std::vector<int>(P.row.begin(), P.row.begin() + nf + 1),
+                          has_blocks, P.off_ptr, P.off_pairs);
+  P.cam_ptr.clear();
+  P.cam_pairs.clear();
+  if (nc > 0) {
+    // per camera its pairs; per border block (n_frames + c, j) the pairs of c that touch j — the rows in order, so the
+    // lists continue the keyframes' CSR
+    std::vector<int> pair_cam(np);
+    for (int p = 0; p < np; ++p) pair_cam[p] = has_blocks(p) ? in.frame_cam[in.pair_target[p]] : -1;
+    P.cam_ptr.assign(nc + 1, 0);
+    for (int p = 0; p < np; ++p)
+      if (pair_cam[p] >= 0) ++P.cam_ptr[pair_cam[p] + 1];
+    csr_prefix(P.cam_ptr);
+    P.cam_pairs.resize(P.cam_ptr[nc]);
+    std::vector<int> at(P.cam_ptr.begin(), P.cam_ptr.end() - 1);
+    for (int p = 0; p < np; ++p)
+      if (pair_cam[p] >= 0) P.cam_pairs[at[pair_cam[p]]++] = p;
+    P.off_ptr.resize(P.n_sky + 1);
+    std::vector<std::vector<int>> per(nf);
+    for (int c = 0; c < nc; ++c) {
+      for (auto& v : per) v.clear();
+      for (int k = P.cam_ptr[c]; k < P.cam_ptr[c + 1]; ++k) {
+        const int p = P.cam_pairs[k];
+        per[in.pair_host[p]].push_back(2 * p);
+        per[in.pair_target[p]].push_back(2 * p + 1);
+      }
+      for (int j = 0; j < N; ++j) {
+        const int s = sky(nf + c, j);
+        if (j < nf) P.off_pairs.insert(P.off_pairs.end(), per[j].begin(), per[j].end());
+        P.off_ptr[s + 1] = (int)P.off_pairs.size();
+        if (j == nf + c) break;
+      }
+    }
+  }
   // Schur terms per skyline block and entries per keyframe: two passes over the points' entries (count, fill)
-  auto frame_of = [&](int e) { return e < 0 ? in.point_host[~e] : target_of(e); };
+  // (the block row of an entry: a keyframe, or n_frames + the camera of a camera part)
+  auto frame_of = [&](int e) {
+    return e < 0 ? in.point_host[~e] : e < nb ? target_of(e) : nf + in.frame_cam[target_of(e - nb)];
+  };
   P.term_ptr.assign(P.n_sky + 1, 0);
-  P.fe_ptr.assign(nf + 1, 0);
+  P.fe_ptr.assign(N + 1, 0);
   std::vector<int> at_t, at_f;
   std::vector<int> ent;
   for (int pass = 0; pass < 2; ++pass) {
@@ -57,6 +97,7 @@ bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
       ent.clear();
       ent.push_back(~q);
       for (int k = P.pt_ptr[q]; k < P.pt_ptr[q + 1]; ++k) ent.push_back(P.pt_blocks[k]);
+      for (int k = P.pt_ptr[q]; nc > 0 && k < P.pt_ptr[q + 1]; ++k) ent.push_back(nb + P.pt_blocks[k]);
       for (int a : ent) {
         const int fa = frame_of(a);
         if (pass == 0) ++P.fe_ptr[fa + 1];
@@ -74,7 +115,7 @@ bool build_joint_plan(const JointPlanInput& in, JointPlan& P) {
       csr_prefix(P.term_ptr);
       csr_prefix(P.fe_ptr);
       P.terms.resize(P.term_ptr[P.n_sky]);
-      P.fe_entries.resize(P.fe_ptr[nf]);
+      P.fe_entries.resize(P.fe_ptr[N]);
       at_t.assign(P.term_ptr.begin(), P.term_ptr.end() - 1);
       at_f.assign(P.fe_ptr.begin(), P.fe_ptr.end() - 1);
     }

@@ -211,6 +211,8 @@ def lib(path: Optional[str] = None):
         "pba_joint_step": ([vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i32)], C.c_int),
         "pba_joint_get_reduced_system": ([vp, vp, vp], C.c_int),
         "pba_joint_get_step": ([vp, vp, vp], C.c_int),
+        "pba_joint_set_solve_intrinsics": ([vp, i32], C.c_int),
+        "pba_joint_get_intrinsics_step": ([vp, vp], C.c_int),
         "pba_joint_candidate_cost": ([vp, C.POINTER(C.c_double)], C.c_int),
         "pba_joint_accept": ([vp], C.c_int),
         "pba_solve_joint": ([vp, C.POINTER(SolverOptions), C.POINTER(SolverSummary)], C.c_int),
@@ -712,7 +714,7 @@ class Engine:
 
     def joint_get_reduced_system(self):
         """(S (8·n_frames square, the last step's: damped, constants as identity rows), g_S); unknowns per keyframe
-        [δpose (6) | δa δb]."""
+        [δpose (6) | δa δb]; with joint_set_solve_intrinsics 8·(n_frames + n_cams), the cameras' δk behind them."""
         n = self.joint_system_size()
         S, g = np.empty((n, n), np.float64), np.empty(n, np.float64)
         self._ck(self._L.pba_joint_get_reduced_system(self._h, _p(S), _p(g)), "pba_joint_get_reduced_system")
@@ -723,6 +725,18 @@ class Engine:
         dk, dr = np.empty((self.n_frames, 8), np.float64), np.empty(self.n_points, np.float64)
         self._ck(self._L.pba_joint_get_step(self._h, _p(dk), _p(dr)), "pba_joint_get_step")
         return dk, dr
+
+    def joint_set_solve_intrinsics(self, enable: bool = True):
+        """With set_optimize_intrinsics and set_affine_brightness both on (set_intrinsics_with_affine): joint_* and
+        solve_joint free the intrinsics state too — 8 unknowns per camera behind the keyframes' (joint_system_size is
+        8·(n_frames + n_cams)), joint_accept moves the intrinsics state.  Off by default (those entry points refuse)."""
+        self._ck(self._L.pba_joint_set_solve_intrinsics(self._h, int(bool(enable))), "pba_joint_set_solve_intrinsics")
+
+    def joint_get_intrinsics_step(self) -> np.ndarray:
+        """δk of the cameras (n_cams, 8) of the last step, with respect to the level-0 intrinsics state."""
+        dk = np.empty((self._n_cams, 8), np.float64)
+        self._ck(self._L.pba_joint_get_intrinsics_step(self._h, _p(dk)), "pba_joint_get_intrinsics_step")
+        return dk
 
     def joint_candidate_cost(self) -> float:
         c = C.c_double()
